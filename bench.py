@@ -5,12 +5,15 @@ synthetic inputs already resident in HBM.
     python bench.py --gpus N --steps K --warmup W            (N > 1 without WORLD_SIZE: starts its own N rank processes)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
+    python bench.py --full                                   (every diagnostic leg below as well)
+    python bench.py --dump-outputs DIR                       (what the last timed step computed, as DIR/<name>.npy)
 
 A "step" = forward (train mode, dropout 0.1) + BCE x NA loss + backward + [RCCL gradient exchange] +
 clip_grad_norm_(5.) + BertAdam + re-cast of the weight operand copies: everything tasks/gqa_conf.py:174-202 does per batch.
 Rank 0 prints ONE JSON line.  The headline (`value`, `dtype` "bf16x3_fwd") is the mode whose logits stay inside the north star's
 1e-3 bound - the forward pass on split-f32 operands (three bf16 MFMA products per f32 product), the backward pass in bf16 as
-BASELINE config 3 prescribes - with its logits error re-measured in-run against the CPU oracle (`parity_in_run`).  The same line
+BASELINE config 3 prescribes.  A plain run sets up, warms up, times the steps, writes its outputs (--dump-outputs) and prints the
+line.  With --full it also re-measures the headline's logits error against the CPU oracle (`parity_in_run`), and the line
 carries `config3_bf16` (bf16 forward too: faster, logits OUTSIDE the bound, its error next to it), `tolerance_compliant` (bf16x3
 throughout), `seq30` (T = 30, what tasks/gqa_model.py:11 pads to), `forward_only_b256` (BASELINE config 2), `dropin_step` (the
 reference trainer's own statements through GQAModel / BertAdam on fresh batches from the device batcher), BASELINE configs 4 and 5
@@ -359,7 +362,9 @@ def launch_check(world, rank, fail_rank, fail_mode):
         raise SystemExit(3)
     if world > 1:
         import datetime
-        dist.init_process_group("gloo", timeout=datetime.timedelta(seconds=60))
+        # under a launcher every rank supervises its own child: a rank whose first attempt failed at once starts its fallback attempt up to one
+        # rendezvous timeout before the others give up on theirs, so a fallback attempt waits twice as long for them
+        dist.init_process_group("gloo", timeout=datetime.timedelta(seconds=120 if os.environ.get("RGQA_BENCH_DP_FALLBACK") else 60))
     t = torch.ones(1)
     if world > 1:
         dp_selfcheck(dist, "allreduce" if mode.startswith("sharded") else mode, torch.device("cpu"), "f32")      # (gloo has no all_to_all on CPU tensors in every build)
@@ -384,6 +389,27 @@ def time_steps(fn, n, warm):
         fn()
     torch.cuda.synchronize()
     return (time.perf_counter() - t0) / n * 1e3
+
+
+DUMP_SAMPLE = 1 << 21        # --dump-outputs: arena positions at which the weights and gradients are written (8 MB each in f32)
+
+
+def dump_outputs(path, e, last, world):
+    """--dump-outputs: what the last timed step handed its caller, as <path>/<name>.npy in f32 (about 18 MB at B=256): the forward pass's
+    logits and pooled features, the loss, and the updated weights and their gradients at DUMP_SAMPLE arena positions drawn with numpy seed 0
+    (the same positions in every run of the same workload).  Under an exchange (N > 1) the optimizer state is sharded over the ranks: rank 0
+    writes the logits, pooled features and loss of its own batch only."""
+    os.makedirs(path, exist_ok=True)
+    lg, pl, loss = last
+    arrays = {"logits": lg, "pooled": pl, "loss": loss}
+    if world == 1:
+        idx = np.sort(np.random.RandomState(0).randint(0, e.arena_elems, size=min(DUMP_SAMPLE, e.arena_elems)))
+        it = torch.from_numpy(idx).to(e.device)
+        arrays["weights_sample"] = e.params[it]         # (the arena getters wait for an optimizer pass still beside the stream)
+        arrays["grads_sample"] = e.grads[it]
+    for name, v in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), v.detach().float().cpu().numpy())
+    note("outputs of the last timed step written to %s (%s)" % (path, ", ".join(sorted(arrays))))
 
 
 def probe_sustained_clock(e):
@@ -580,8 +606,17 @@ def main():
     ap.add_argument("--launch-check", action="store_true", help=argparse.SUPPRESS)          # CPU rehearsal of the N-rank launch path
     ap.add_argument("--launch-check-fail-rank", type=int, default=-1, help=argparse.SUPPRESS)
     ap.add_argument("--launch-check-fail-mode", default="", help=argparse.SUPPRESS)        # fail only under this RGQA_DP_MODE
+    ap.add_argument("--full", action="store_true",
+                    help="every measurement beside the headline as well: the padded-layout leg, live per-kernel timing and the roofline, the bf16 / bf16x3 / "
+                         "forward-only / T=30 / drop-in / config 4 and 5 legs, the CPU baseline with its logits check, and (N > 1) the exchange legs.  "
+                         "--no-cpu-baseline, --cpu-sample, --profile-steps and --no-extra-legs shape such a run; without --full a run only sets up, "
+                         "warms up, times the steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (f32): logits, pooled features, loss "
+                         "and, on one GPU, the updated weights and gradients at a fixed, seeded sample of arena positions")
     args = ap.parse_args()
-    if args.lean:
+    full = args.full and not args.lean
+    if not full:
         args.no_cpu_baseline, args.profile_steps = True, 0
 
     child = os.environ.get("RGQA_BENCH_CHILD") == "1"
@@ -682,7 +717,7 @@ def main():
     e.sync_weights()
     comm = make_exchange(e, dist, mode=dp_mode) if dist is not None else None      # RGQA_DP_MODE: sharded (default, payload by precision) | allreduce (f32; _bf16 opts in) (rgqa_amd/parallel.py)
     dp_wire = None
-    if dist is not None and dist.get_backend() == "nccl" and not args.lean:
+    if dist is not None and dist.get_backend() == "nccl" and not args.lean:      # (not a --full leg: it picks the exchange that the timed steps run)
         note("dp_wire: collectives of the exchange on the real chunk sizes")
         dp_wire = dp_wire_probe(dist, comm, torch.device("cuda", local))
     if (dp_wire is not None and (world > 1 or os.environ.get("RGQA_BENCH_RCCL_REHEARSAL") == "1") and dp_mode.partition("_")[0] == "sharded" and "all_to_all" in dp_wire and os.environ.get("RGQA_DP_PEER_PROBE", "1") != "0"
@@ -746,8 +781,9 @@ def main():
         i = state["step"]
         if args.mixup:
             mixup_batch()
-        e.forward(dev["feats"], dev["boxes"], dev["input_ids"], dev["input_mask"], dev["segment_ids"], train=True, seed=4321 + rank + 1000003 * i, lengths=state["lengths"])
-        e.loss_backward(dev["target"])
+        lg, pl = e.forward(dev["feats"], dev["boxes"], dev["input_ids"], dev["input_mask"], dev["segment_ids"], train=True, seed=4321 + rank + 1000003 * i, lengths=state["lengths"])
+        loss = e.loss_backward(dev["target"])
+        state["last"] = (lg, pl, loss)          # engine-owned buffers: what the caller of the step receives (--dump-outputs)
         lr_t = 1e-5 * warmup_linear(i / t_total, 0.1)
         c = state["comm"]
         if c is not None and exchange:
@@ -780,6 +816,8 @@ def main():
     ms = dt / args.steps * 1e3
     value = B * world * args.steps / dt
     n_ranks_seen = dist.get_world_size() if dist is not None else 1
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, e, state["last"], world)
 
     def timed_leg(n, **kw):
         """n more steps, bracketed like the timed region; max over ranks, ms per step"""
@@ -798,7 +836,7 @@ def main():
     # diagnostics outside the timed region (every rank takes part): the same exchange issued after backward instead of beside it, and
     # the step without any exchange -> what the exchange costs beyond what backward hides; the reference's padded layout
     dp_legs = None
-    if dist is not None and not args.lean:
+    if dist is not None and full:
         n2 = max(3, min(args.steps, 40))       # (10 until round 5: a leg that short carries its own start-up and drain, +0.3..0.6 ms per step)
         dp_legs = {"mode": comm.describe(), "ms_per_step": round(ms, 3)}
         comm.release()                               # every rank holds the full optimizer state again
@@ -822,7 +860,7 @@ def main():
             dp_legs["alt_exposed_comm_ms"] = round(dp_legs["alt_ms_per_step"] - local_ms, 3)
     state["comm"] = None          # everything below runs on rank-local state (replicas may diverge from here on: nothing is exchanged again)
     padded_leg = None
-    if lengths is not None and not (args.butd or args.uniter or args.mixup or args.lean):
+    if lengths is not None and full and not (args.butd or args.uniter or args.mixup):
         n2 = max(3, min(args.steps, 40))       # (10 until round 5: a leg that short carries its own start-up and drain, +0.3..0.6 ms per step)
         state["lengths"] = None
         for _ in range(2):
@@ -838,7 +876,7 @@ def main():
     roof = None
     prof = None
     blocks = None
-    if rank == 0:
+    if rank == 0 and args.profile_steps > 0:
         note("live per-launch timing (%d steps)" % args.profile_steps)
         if hasattr(e, "join_update"):
             e.join_update()
@@ -910,7 +948,7 @@ def main():
         dist.barrier()
 
     HEAD = "bf16x3_fwd"
-    extra_legs = rank == 0 and world == 1 and not (args.no_extra_legs or args.lean or args.butd or args.uniter or args.mixup or args.padded) and args.precision == HEAD
+    extra_legs = rank == 0 and world == 1 and full and not (args.no_extra_legs or args.butd or args.uniter or args.mixup or args.padded) and args.precision == HEAD
     cfg3 = tol = seq30 = fwd_only = dropin = other = parity = None
     engines = {args.precision: e}
     if extra_legs:

@@ -450,6 +450,26 @@ def test_bench_profiling_section_has_no_collective():
     assert "if c is not None and exchange:" in src
 
 
+def test_bench_dump_outputs_writes_the_last_step_in_f32(tmp_path):
+    """bench.py --dump-outputs: the last step's logits, pooled features and loss, and the weights and gradients at the same fixed, seeded
+    arena positions in every run, as f32 .npy files within 64 MB; on a CPU stand-in for the engine (the arenas are plain tensors)."""
+    import bench
+    n = 3_000_000
+    e = types.SimpleNamespace(arena_elems=n, device=torch.device("cpu"), params=torch.arange(n, dtype=torch.float32), grads=-torch.arange(n, dtype=torch.float32))
+    last = (torch.randn(4, 7), torch.randn(4, 3), torch.full((1,), 2.5))
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), e, last, 1)
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == ["grads_sample.npy", "logits.npy", "loss.npy", "pooled.npy", "weights_sample.npy"]
+    got = {f: np.load(str(tmp_path / "a" / f)) for f in files}
+    assert all(v.dtype == np.float32 for v in got.values()) and sum(v.nbytes for v in got.values()) <= 64 << 20
+    assert all(np.array_equal(v, np.load(str(tmp_path / "b" / f))) for f, v in got.items())
+    assert np.array_equal(got["logits.npy"], last[0].numpy()) and got["loss.npy"][0] == 2.5
+    assert got["weights_sample.npy"].size == bench.DUMP_SAMPLE and np.array_equal(got["grads_sample.npy"], -got["weights_sample.npy"])
+    bench.dump_outputs(str(tmp_path / "n2"), e, last, 2)          # under an exchange: the rank's own logits, pooled features and loss only
+    assert sorted(os.listdir(tmp_path / "n2")) == ["logits.npy", "loss.npy", "pooled.npy"]
+
+
 def test_committed_bench_line_keeps_the_contract():
     """The JSON line the driver parses (profiles/rNN_bench_n1.json = bench.py's stdout on an MI355X): every field of the contract, the
     metric / workload BASELINE.json names, roofline consistency (achieved / peak = frac; flops per launch / mean launch duration = achieved)

@@ -6,7 +6,7 @@ python3 -c "from rgqa_amd import _lib; _lib.load()" || { echo "stale library in 
 for m in "--mixup" "--uniter" "--butd" "--precision bf16x3_fwd" "--precision bf16x3" "--padded" ""; do
   for dp in sharded allreduce; do
     tag=$(echo "$m" | tr -d ' -'); tag=${tag:-headline}
-    RGQA_DP_MODE=$dp RGQA_BENCH_RCCL_REHEARSAL=1 timeout -k 10 300 python3 bench.py $m --steps 12 --warmup 4 --no-cpu-baseline --no-extra-legs > $OUT/s14_${tag}_$dp.json 2> $OUT/s14_${tag}_$dp.err; rc=$?
+    RGQA_DP_MODE=$dp RGQA_BENCH_RCCL_REHEARSAL=1 timeout -k 10 300 python3 bench.py --full $m --steps 12 --warmup 4 --no-cpu-baseline --no-extra-legs > $OUT/s14_${tag}_$dp.json 2> $OUT/s14_${tag}_$dp.err; rc=$?
     echo "$tag/$dp rc=$rc $(python3 -c "
 import json,sys
 try:

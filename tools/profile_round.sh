@@ -34,7 +34,7 @@ else
   echo "pmc traffic: a pass failed - profiles/${TAG}_pmc_gemm_nt.json left as it was"
 fi
 # 2. the headline line (live HIP-event roofline, tolerance_compliant / tolerance_compliant_fwd / forward-only / drop-in legs, CPU baseline)
-python3 bench.py > $OUT/${TAG}_bench_n1.json 2> $OUT/${TAG}_bench_n1.err; echo "bench rc=$?"
+python3 bench.py --full > $OUT/${TAG}_bench_n1.json 2> $OUT/${TAG}_bench_n1.err; echo "bench rc=$?"
 stamp $OUT/${TAG}_bench_n1.json
 # 3. kernel trace + stats: shipped two-stream configuration, and wgrad serialised (what bench.py's live timing sees), three precisions
 run() { name=$1; shift; ( "$@" ) > $OUT/${TAG}_$name.log 2>&1; echo "$name rc=$?"; }

@@ -32,7 +32,7 @@ for fam in x3fwd bf16; do
   rm -rf $OUT/${TAG}_p_${fam}_FETCH_SIZE $OUT/${TAG}_p_${fam}_WRITE_SIZE
 done
 # 2. the driver's line (live HIP-event roofline, every leg, CPU baseline)
-python3 bench.py --steps 20 --warmup 5 > $OUT/${TAG}_bench_n1.json 2> $OUT/${TAG}_bench_n1.err; echo "bench rc=$?"
+python3 bench.py --full --steps 20 --warmup 5 > $OUT/${TAG}_bench_n1.json 2> $OUT/${TAG}_bench_n1.err; echo "bench rc=$?"
 stamp $OUT/${TAG}_bench_n1.json
 # 3. kernel trace + stats: the shipped multi-stream configuration and the serialised one, three precisions
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/${TAG}_p_stats -- $BENCH > $OUT/${TAG}_stats.log 2>&1; echo "stats rc=$?"
