@@ -31,7 +31,9 @@ extern "C" {
                                    with the backward pass of RGQA_PRECISION_BF16 (BASELINE config 3 prescribes a bf16 backward): the forward
                                    kernels leave a bf16 image of every tensor the backward reads beside the split-f32 one.  Gradients carry bf16
                                    rounding (held to the bf16 mode's loss / gradient-norm / sampled-gradient gates), weights, moments and the
-                                   optimizer stay f32.  Operand copies: params_lp split f32 (4 B / element), params_lp_t bf16 (2 B / element). */
+                                   optimizer stay f32.  Operand copies: params_lp split f32 (4 B / element), params_lp_t bf16 (2 B / element).
+                                   arch 0 and 2 as RGQA_PRECISION_BF16X3; arch 1 (BUTD): hidden multiple of 64, the forward of the bf16x3 BUTD
+                                   engine except its GRU recurrence, which runs as one persistent split-f32 launch where key 18 allows (below) */
 
 typedef struct rgqa_config {
     int32_t vocab_size, hidden, heads, inter, max_pos, type_vocab; /* BertConfig, lxrt/modeling.py:172-258 */
@@ -64,7 +66,9 @@ int rgqa_version(void);
  * key 16: 0 launches the two attention problems of a stage separately, 1 as one launch (default); key 17: gradient-buffer sets planned by
  * the NEXT rgqa_engine_bind (2 x key 6 .. 8; 0 = that minimum); key 18: 0 = the BUTD engine's GRU recurrence as one GEMM + one gate kernel per
  * token from the host, 1 = one persistent launch per direction (bf16, hidden 1024, B <= 256): 64-sample row groups x 16-unit slices, W_hh slice
- * in LDS, 4 waves, 2 = the same with 8 waves, 3 (default) = 32-sample row groups x 32-unit slices, weights in registers, 8 waves;
+ * in LDS, 4 waves, 2 = the same with 8 waves, 3 (default) = 32-sample row groups x 32-unit slices, weights in registers, 8 waves; the
+ * bf16x3_fwd BUTD engine's forward recurrence: any non-zero value = one persistent split-f32 launch (32-sample row groups x 32-unit slices), 0 = the
+ * host-driven loop of the bf16x3 engine;
  * key 19: 1 = the bf16 engine's LayerNorms behind the attention-output / FFN-output projections are done inside the projection's launch by the
  * workgroup that finishes a row block last, 0 (default: same step time) = separate LayerNorm launches; bit-identical results either way;
  * key 20: cap on the grid of the (grid-stride) BertAdam kernel, default 2048 workgroups (with the update beside the forward pass a smaller grid

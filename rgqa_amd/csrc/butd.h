@@ -13,11 +13,17 @@ struct WnDesc {
     int out, in, kp, op;
     int blk0, nblk, tile0, tiles_x, tiles_y;
 };
+// elem: 0 f32, 1 bf16, 2 split f32, 3 split-f32 eff with a bf16 efft (bf16x3_fwd: the forward GEMMs read eff, the bf16 backward efft)
 int kb_wn_forward_group(const WnDesc* descs_dev, int nd, int total_blocks, int total_tiles, float* partial, int elem, hipStream_t s);
 int kb_wn_backward_group(const WnDesc* descs_dev, int nd, int total_blocks, float* partial, hipStream_t s);
 template <typename T> int kb_embed_fwd(const int64_t* toks, const float* table, T* out, int rows, int E, int Ep, hipStream_t s);
 template <typename T> int kb_embed_bwd(const int64_t* toks, const T* dx, float* dtable, int rows, int E, int Ep, int pad_idx, hipStream_t s);
 template <typename T> int kb_gru_fwd(const T* gi, long ldgi, const T* gh, const T* hprev, T* hnew, T* rs, T* zs, T* ns, T* ghn, int B, int H, hipStream_t s);
+// bf16x3_fwd, host-driven recurrence: the gates of kb_gru_fwd<sf32> (same arithmetic), h_t also as its bf16 image, the saved gates in bf16
+int kb_gru_fwd_x3img(const sf32* gi, long ldgi, const sf32* gh, const sf32* hprev, sf32* hnew, bf16_t* himg, bf16_t* rs, bf16_t* zs, bf16_t* ns, bf16_t* ghn,
+                     int B, int H, hipStream_t s);
+// bf16x3_fwd: the image features in split f32 and their bf16 image in one pass
+int kb_concat_x3img(const float* feat, const float* pos, sf32* out, bf16_t* img, int rows, int F, int Pd, int Dp, hipStream_t s);
 template <typename T> int kb_gru_bwd(const T* dh, const T* hprev, const T* rs, const T* zs, const T* ns, const T* ghn, T* dgi, long lddgi, T* dgh, T* dhprev, int B, int H, hipStream_t s);
 template <typename T> int kb_concat(const float* feat, const float* pos, T* out, int rows, int F, int Pd, int Dp, hipStream_t s);
 template <typename T> int kb_attend_fwd(const T* ip, const T* qp, const float* wlin, const float* blin, const T* imgf, float* att, T* img_enc, int B, int O, int H, int Dp, DropCfg drop, hipStream_t s);
@@ -36,5 +42,10 @@ bool gru_persist_ok(int B, int H);
 size_t gru_persist_counter_ints(int B, int L);
 int k_gru_fwd_persist(const bf16_t* GI, long ldgi, const bf16_t* W, int ldw, const float* bhh, bf16_t* Hall, bf16_t* Rg, bf16_t* Zg, bf16_t* Ng, bf16_t* GHN,
                       int B, int L, int H, int* counters, hipStream_t s);
+// split-f32 forward of the bf16x3_fwd precision (butd_gru.hip gru_fwd_persist_x3_kernel): Hall split f32, its bf16 image Himg and the saved gates
+// bf16; same counters.  gru_persist_x3_ok: key 18 != 0, H = 1024, B <= 256, the grid fits the CUs and one block per CU is resident
+bool gru_persist_x3_ok(int B, int H);
+int k_gru_fwd_persist_x3(const sf32* GI, long ldgi, const sf32* W, int ldw, const float* bhh, sf32* Hall, bf16_t* Himg, bf16_t* Rg, bf16_t* Zg, bf16_t* Ng,
+                         bf16_t* GHN, int B, int L, int H, int* counters, hipStream_t s);
 int k_gru_bwd_persist(const bf16_t* dH, const bf16_t* Hall, const bf16_t* Rg, const bf16_t* Zg, const bf16_t* Ng, const bf16_t* GHN, bf16_t* dGI, long lddgi, bf16_t* dGH,
                       const bf16_t* WT, int ldwt, int B, int L, int H, int* counters, hipStream_t s);

@@ -31,23 +31,33 @@ struct BLin {            // one linear layer: V (or W) [out, in], optional scala
     int norm;            // index of its ||V||^2 scalar
 };
 
-template <typename T>
+// T = type of the activations the FORWARD pass computes in (and of the direct effective-weight copy).  MIXED (T = sf32 only; rgqa.h
+// RGQA_PRECISION_BF16X3_FWD): the forward pass of the bf16x3 engine, the backward pass of the bf16 engine - TB = bf16_t is the type of every gradient
+// buffer, of the transposed effective-weight copy (dgrad, the persistent GRU backward), of the saved GRU gates, and of a bf16 IMAGE of every forward
+// tensor the backward reads (X, Hall, IF, IP, QP, IE, QR, IR, J, C1: separate buffers, written by the launch that produces the tensor where it can -
+// GEMM epilogues through GemmProblem::Cb, the GRU gates, the feature concat - and by k_sf_image for X, IE and J).  The GRU recurrence runs as one
+// persistent split-f32 launch (butd_gru.hip gru_fwd_persist_x3_kernel) where gru_persist_x3_ok allows, else the bf16x3 engine's host-driven loop.
+template <typename T, bool MIXED = false>
 class ButdEngine : public EngineBase {
 public:
+    static_assert(!MIXED || std::is_same<T, sf32>::value, "the mixed precision is a split-f32 forward with a bf16 backward");
+    using TB = typename std::conditional<MIXED, bf16_t, T>::type;
     static constexpr bool LP = !std::is_same<T, float>::value;
     static constexpr bool X3 = std::is_same<T, sf32>::value;       // split-f32 activations and effective-weight copies (bf16x3 precision)
     // row pitches / padded contraction lengths: multiples of 64 elements for the low-precision engines - whole K-steps of the LDS-DMA GEMM kernels
     // (until round 5 bf16 padded to 8: K = 304 (GloVe), 2056 (RoI features + box) and 1848 (answers) sent four GEMMs of the step to the 128 x 128
     // register-staged kernel, 0.38 ms) and whole 128-byte lines of split f32
     static constexpr int LDM = LP ? 64 : 8;
-    static int nt_gemm(GemmGroup& g, int out_f32, int trans_b, hipStream_t s) {
-        if constexpr (X3) return launch_gemm_nt_x3(g, out_f32, s);
-        else if constexpr (LP) return launch_gemm_nt_bf16(g, out_f32, s);
+    template <typename U> static int nt_gemm_t(GemmGroup& g, int out_f32, int trans_b, hipStream_t s) {
+        if constexpr (std::is_same<U, sf32>::value) return launch_gemm_nt_x3(g, out_f32, s);
+        else if constexpr (std::is_same<U, bf16_t>::value) return launch_gemm_nt_bf16(g, out_f32, s);
         else return launch_gemm_f32(g, 0, trans_b, s);
     }
+    static int nt_gemm(GemmGroup& g, int out_f32, int trans_b, hipStream_t s) { return nt_gemm_t<T>(g, out_f32, trans_b, s); }
+    static int nt_gemm_b(GemmGroup& g, int out_f32, int trans_b, hipStream_t s) { return nt_gemm_t<TB>(g, out_f32, trans_b, s); }      // dgrad
     static int tn_gemm(GemmGroup& g, hipStream_t s) {
-        if constexpr (X3) return launch_gemm_tn_x3(g, s);
-        else if constexpr (LP) return launch_gemm_tn_bf16(g, 1, s);
+        if constexpr (std::is_same<TB, sf32>::value) return launch_gemm_tn_x3(g, s);
+        else if constexpr (std::is_same<TB, bf16_t>::value) return launch_gemm_tn_bf16(g, 1, s);
         else return launch_gemm_f32(g, 1, 1, s);
     }
     size_t emb = 0;
@@ -62,10 +72,13 @@ public:
     // workspace
     float *c3_bias_pad = nullptr;        // bf16x3: ans_classifier.3.bias zero-padded to op entries
     float *sumsq = nullptr, *sumsq_scr = nullptr, *partial = nullptr, *wlin_eff = nullptr, *att = nullptr, *logits = nullptr, *dwscr = nullptr, *dw_part = nullptr, *db_part = nullptr, *loss_dev = nullptr;
-    T *X = nullptr, *GI = nullptr, *GH = nullptr, *Hall = nullptr, *Rg = nullptr, *Zg = nullptr, *Ng = nullptr, *GHN = nullptr;
-    T *IF = nullptr, *IP = nullptr, *QP = nullptr, *IE = nullptr, *QR = nullptr, *IR = nullptr, *J = nullptr, *C1 = nullptr, *dlogits = nullptr;
-    T *dC1 = nullptr, *dJ = nullptr, *dQR = nullptr, *dIR = nullptr, *dIE = nullptr, *dIP = nullptr, *dQP = nullptr, *dq = nullptr, *dHa = nullptr, *dHb = nullptr,
-      *dGI = nullptr, *dGH = nullptr, *dX = nullptr, *tmpH = nullptr;
+    T *X = nullptr, *GI = nullptr, *GH = nullptr, *Hall = nullptr;
+    TB *Rg = nullptr, *Zg = nullptr, *Ng = nullptr, *GHN = nullptr;
+    T *IF = nullptr, *IP = nullptr, *QP = nullptr, *IE = nullptr, *QR = nullptr, *IR = nullptr, *J = nullptr, *C1 = nullptr;
+    // what the backward pass reads in place of each forward tensor: its bf16 image (MIXED) or the tensor itself
+    TB *Xb = nullptr, *Hb = nullptr, *IFb = nullptr, *IPb = nullptr, *QPb = nullptr, *IEb = nullptr, *QRb = nullptr, *IRb = nullptr, *Jb = nullptr, *C1b = nullptr;
+    TB *dlogits = nullptr, *dC1 = nullptr, *dJ = nullptr, *dQR = nullptr, *dIR = nullptr, *dIE = nullptr, *dIP = nullptr, *dQP = nullptr, *dq = nullptr, *dHa = nullptr,
+       *dHb = nullptr, *dGI = nullptr, *dGH = nullptr, *dX = nullptr, *tmpH = nullptr;
 
     explicit ButdEngine(const rgqa_config& c) {
         cfg = c;
@@ -122,19 +135,26 @@ public:
           partial = take<float>(partial_floats); }      // (column-sum scratch; also the hot words' partial sums of the embedding gradient: csrc/embed.hip)
         for (BLin* l : lins) {
             l->eff = ws_used; take<T>((size_t)l->op * l->kp);          // op >= out rows: the rows past `out` stay zero (bf16x3: the logits GEMM runs over op columns)
-            l->efft = ws_used; take<T>((size_t)l->kp * l->op);
+            l->efft = ws_used; take<TB>((size_t)l->kp * l->op);
         }
         wlin_eff = take<float>(H); c3_bias_pad = take<float>(c3.op);
         X = take<T>((size_t)B * L * Ep); GI = take<T>((size_t)B * L * 3 * H); GH = take<T>((size_t)B * 3 * H);
         Hall = take<T>((size_t)(L + 1) * B * H);
-        Rg = take<T>((size_t)L * B * H); Zg = take<T>((size_t)L * B * H); Ng = take<T>((size_t)L * B * H); GHN = take<T>((size_t)L * B * H);
+        Rg = take<TB>((size_t)L * B * H); Zg = take<TB>((size_t)L * B * H); Ng = take<TB>((size_t)L * B * H); GHN = take<TB>((size_t)L * B * H);
         IF = take<T>((size_t)B * O * Dp); IP = take<T>((size_t)B * O * H); QP = take<T>((size_t)B * H); att = take<float>((size_t)B * O);
         IE = take<T>((size_t)B * Dp); QR = take<T>((size_t)B * H); IR = take<T>((size_t)B * H); J = take<T>((size_t)B * H); C1 = take<T>((size_t)B * 2 * H);
-        logits = take<float>((size_t)B * NAp); dlogits = take<T>((size_t)B * NAp);
-        dC1 = take<T>((size_t)B * 2 * H); dJ = take<T>((size_t)B * H); dQR = take<T>((size_t)B * H); dIR = take<T>((size_t)B * H); dIE = take<T>((size_t)B * Dp);
-        dIP = take<T>((size_t)B * O * H); dQP = take<T>((size_t)B * H); dq = take<T>((size_t)B * H); dHa = take<T>((size_t)B * H); dHb = take<T>((size_t)B * H);
-        tmpH = take<T>((size_t)B * H);
-        dGI = take<T>((size_t)B * L * 3 * H); dGH = take<T>((size_t)L * B * 3 * H); dX = take<T>((size_t)B * L * Ep);
+        if constexpr (MIXED) {
+            Xb = take<TB>((size_t)B * L * Ep); Hb = take<TB>((size_t)(L + 1) * B * H); IFb = take<TB>((size_t)B * O * Dp); IPb = take<TB>((size_t)B * O * H);
+            QPb = take<TB>((size_t)B * H); IEb = take<TB>((size_t)B * Dp); QRb = take<TB>((size_t)B * H); IRb = take<TB>((size_t)B * H); Jb = take<TB>((size_t)B * H);
+            C1b = take<TB>((size_t)B * 2 * H);
+        } else {
+            Xb = X; Hb = Hall; IFb = IF; IPb = IP; QPb = QP; IEb = IE; QRb = QR; IRb = IR; Jb = J; C1b = C1;
+        }
+        logits = take<float>((size_t)B * NAp); dlogits = take<TB>((size_t)B * NAp);
+        dC1 = take<TB>((size_t)B * 2 * H); dJ = take<TB>((size_t)B * H); dQR = take<TB>((size_t)B * H); dIR = take<TB>((size_t)B * H); dIE = take<TB>((size_t)B * Dp);
+        dIP = take<TB>((size_t)B * O * H); dQP = take<TB>((size_t)B * H); dq = take<TB>((size_t)B * H); dHa = take<TB>((size_t)B * H); dHb = take<TB>((size_t)B * H);
+        tmpH = take<TB>((size_t)B * H);
+        dGI = take<TB>((size_t)B * L * 3 * H); dGH = take<TB>((size_t)L * B * 3 * H); dX = take<TB>((size_t)B * L * Ep);
         size_t mw = 0;
         for (BLin* l : lins) { size_t n = (size_t)l->out * l->kp; if (n > mw) mw = n; }
         dwscr = take<float>(mw); dw_part = take<float>((size_t)B * H); db_part = take<float>(B);
@@ -180,6 +200,7 @@ public:
     }
     int* gru_cnt = nullptr; int* emb_keys = nullptr; size_t partial_floats = 0;
     bool gru_persist() const { if constexpr (LP && !X3) return gru_persist_ok(B, H); else return false; }
+    bool gru_persist_bwd() const { if constexpr (std::is_same<TB, bf16_t>::value) return gru_persist_ok(B, H); else return false; }     // (bf16 and mixed)
     size_t workspace_bytes(int B_, int L_, int O_) override { dry = true; plan(B_, L_, O_); dry = false; return ws_used + 256; }
     int bind(float* p, float* g, void*, void*, void* w, size_t wb, int B_, int L_, int O_) override {
         RGQA_REQUIRE(p != nullptr && w != nullptr, "bind: null parameter arena or workspace");
@@ -196,7 +217,8 @@ public:
     }
     bool eff_zeroed = false;
     T* effp(const BLin& l) const { return reinterpret_cast<T*>(ws + l.eff); }
-    T* efftp(const BLin& l) const { return reinterpret_cast<T*>(ws + l.efft); }
+    TB* efftp(const BLin& l) const { return reinterpret_cast<TB*>(ws + l.efft); }
+    static void* cb(TB* image) { return MIXED ? (void*)image : nullptr; }      // a split-f32 GEMM result's bf16 image (GemmProblem::Cb), MIXED only
 
 #define CKB(x) do { int _r = (x); if (_r) return _r; } while (0)
     int sync_weights(hipStream_t s) override {
@@ -204,7 +226,7 @@ public:
         if (!eff_zeroed) {   // padding rows / columns of the effective copies must be exact zeros
             for (BLin* l : lins) {
                 CKB(rgqa_check_hip(hipMemsetAsync(effp(*l), 0, sizeof(T) * (size_t)l->op * l->kp, s), "zero eff"));
-                CKB(rgqa_check_hip(hipMemsetAsync(efftp(*l), 0, sizeof(T) * (size_t)l->kp * l->op, s), "zero efft"));
+                CKB(rgqa_check_hip(hipMemsetAsync(efftp(*l), 0, sizeof(TB) * (size_t)l->kp * l->op, s), "zero efft"));
             }
             eff_zeroed = true;
         }
@@ -213,7 +235,7 @@ public:
             CKB(rgqa_check_hip(hipMemcpyAsync(wn_dev, wn_host.data(), sizeof(WnDesc) * wn_host.size(), hipMemcpyHostToDevice, s), "weight-norm table"));
             wn_uploaded = true;
         }
-        CKB(kb_wn_forward_group(wn_dev, (int)wn_host.size(), wn_blocks, wn_tiles, wn_partial, X3 ? 2 : (LP ? 1 : 0), s));
+        CKB(kb_wn_forward_group(wn_dev, (int)wn_host.size(), wn_blocks, wn_tiles, wn_partial, MIXED ? 3 : (X3 ? 2 : (LP ? 1 : 0)), s));
         if (LP) {
             CKB(rgqa_check_hip(hipMemsetAsync(c3_bias_pad, 0, sizeof(float) * c3.op, s), "zero padded bias"));
             CKB(rgqa_check_hip(hipMemcpyAsync(c3_bias_pad, P + c3.b, sizeof(float) * c3.out, hipMemcpyDeviceToDevice, s), "padded bias"));
@@ -226,10 +248,10 @@ public:
 
     // ------------------------------------------------------------------ GEMM wrappers (single problem)
     static void ginit(GemmGroup& g) { memset(&g, 0, sizeof g); g.count = 1; g.drop = make_drop(0.f, 0, 0); }
-    int gemm_fwd(const void* x, int ldx, int M, const BLin& l, void* C, int ldc, int epi, int out_f32, DropCfg drop, uint32_t site, hipStream_t s) {
+    int gemm_fwd(const void* x, int ldx, int M, const BLin& l, void* C, int ldc, int epi, int out_f32, DropCfg drop, uint32_t site, hipStream_t s, void* Cb = nullptr) {
         GemmGroup g; ginit(g); g.drop = drop;
         GemmProblem& p = g.p[0];
-        p.A = x; p.lda = ldx; p.B = effp(l); p.ldb = l.kp; p.C = C; p.ldc = ldc; p.M = M; p.N = l.out; p.K = l.kp; p.bias = P + l.b; p.epi = epi; p.drop_site = site;
+        p.A = x; p.lda = ldx; p.B = effp(l); p.ldb = l.kp; p.C = C; p.ldc = ldc; p.Cb = Cb; p.M = M; p.N = l.out; p.K = l.kp; p.bias = P + l.b; p.epi = epi; p.drop_site = site;
         if (M == B) { g.splitk_ws = gemm_ws; g.splitk_floats = gemm_ws_floats; }      // the per-sample GEMMs: skinny whatever the batch (call site, not shape)
         return nt_gemm(g, out_f32, 0, s);
     }
@@ -241,7 +263,7 @@ public:
         if (LP) {
             p.B = efftp(l); p.ldb = l.op; p.K = (int)rupb(l.out, LDM) > l.op ? l.op : (int)rupb(l.out, LDM);
             if (M == B) { g.splitk_ws = gemm_ws; g.splitk_floats = gemm_ws_floats; }
-            return nt_gemm(g, 0, 1, s);
+            return nt_gemm_b(g, 0, 1, s);
         }
         p.B = effp(l); p.ldb = l.kp; p.K = l.out;
         return launch_gemm_f32(g, 0, 1, s);
@@ -254,7 +276,7 @@ public:
         CKB(tn_gemm(g, s));
         CKB(kb_wn_bwd(dwscr, l.kp, P + l.v, l.wn ? P + l.g : nullptr, l.wn ? sumsq + l.norm : nullptr, partial, G + l.v, l.wn ? G + l.g : nullptr, l.out, l.in, accumulate, s));
         // bias gradient: column sums of dy (its padded columns are exact zeros) into scratch, then the first `out` of them
-        CKB(k_colsum<T>((const T*)dy, lddy, partial, dwscr, 0, rows, (int)rupb(l.out, 4), s));
+        CKB(k_colsum<TB>((const TB*)dy, lddy, partial, dwscr, 0, rows, (int)rupb(l.out, 4), s));
         hipLaunchKernelGGL(butd_bias_copy_kernel, dim3(cdiv(l.out, 256)), dim3(256), 0, s, dwscr, G + l.b, l.out, accumulate);
         RGQA_LAUNCH_CHECK("butd_bias_copy_kernel");
         return RGQA_OK;
@@ -272,30 +294,45 @@ public:
         const DropCfg nd = make_drop(0.f, 0, 0);
         CKB(sync_weights(s));
         CKB(kb_embed_fwd<T>(toks, P + emb, X, B * L, E, Ep, s));
+        if constexpr (MIXED) CKB(k_sf_image(X, Ep, Xb, Ep, B * L, Ep, s));
         CKB(gemm_fwd(X, Ep, B * L, wih, GI, 3 * H, EPI_BIAS, 0, nd, 0, s));
         CKB(rgqa_check_hip(hipMemsetAsync(Hall, 0, sizeof(T) * (size_t)B * H, s), "h0"));
+        if constexpr (MIXED) CKB(rgqa_check_hip(hipMemsetAsync(Hb, 0, sizeof(TB) * (size_t)B * H, s), "h0 image"));
         if constexpr (LP && !X3) {
             if (gru_persist()) {      // the whole recurrence in one launch, W_hh resident in LDS (butd_gru.hip)
                 CKB(k_gru_fwd_persist(GI, (long)L * 3 * H, effp(whh), whh.kp, P + whh.b, Hall, Rg, Zg, Ng, GHN, B, L, H, gru_cnt, s));
                 goto gru_done;
             }
         }
+        if constexpr (MIXED) {
+            if (gru_persist_x3_ok(B, H)) {      // one split-f32 launch, W_hh in registers and LDS (butd_gru.hip)
+                CKB(k_gru_fwd_persist_x3(GI, (long)L * 3 * H, effp(whh), whh.kp, P + whh.b, Hall, Hb, Rg, Zg, Ng, GHN, B, L, H, gru_cnt, s));
+                goto gru_done;
+            }
+        }
         for (int t = 0; t < L; ++t) {
             T* hp = Hall + (size_t)t * B * H;
             CKB(gemm_fwd(hp, H, B, whh, GH, 3 * H, EPI_BIAS, 0, nd, 0, s));
-            CKB(kb_gru_fwd<T>(GI + (size_t)t * 3 * H, (long)L * 3 * H, GH, hp, hp + (size_t)B * H, Rg + (size_t)t * B * H, Zg + (size_t)t * B * H,
-                              Ng + (size_t)t * B * H, GHN + (size_t)t * B * H, B, H, s));
+            if constexpr (MIXED)
+                CKB(kb_gru_fwd_x3img(GI + (size_t)t * 3 * H, (long)L * 3 * H, GH, hp, hp + (size_t)B * H, Hb + (size_t)(t + 1) * B * H, Rg + (size_t)t * B * H,
+                                     Zg + (size_t)t * B * H, Ng + (size_t)t * B * H, GHN + (size_t)t * B * H, B, H, s));
+            else
+                CKB(kb_gru_fwd<T>(GI + (size_t)t * 3 * H, (long)L * 3 * H, GH, hp, hp + (size_t)B * H, Rg + (size_t)t * B * H, Zg + (size_t)t * B * H,
+                                  Ng + (size_t)t * B * H, GHN + (size_t)t * B * H, B, H, s));
         }
     gru_done:
         const T* q = Hall + (size_t)L * B * H;
-        CKB(kb_concat<T>(feats, boxes, IF, B * O, cfg.feat_dim, cfg.pos_dim, Dp, s));
-        CKB(gemm_fwd(IF, Dp, B * O, ip, IP, H, EPI_RELU, 0, nd, 0, s));
-        CKB(gemm_fwd(q, H, B, qp, QP, H, EPI_RELU, 0, nd, 0, s));
+        if constexpr (MIXED) CKB(kb_concat_x3img(feats, boxes, IF, IFb, B * O, cfg.feat_dim, cfg.pos_dim, Dp, s));
+        else CKB(kb_concat<T>(feats, boxes, IF, B * O, cfg.feat_dim, cfg.pos_dim, Dp, s));
+        CKB(gemm_fwd(IF, Dp, B * O, ip, IP, H, EPI_RELU, 0, nd, 0, s, cb(IPb)));
+        CKB(gemm_fwd(q, H, B, qp, QP, H, EPI_RELU, 0, nd, 0, s, cb(QPb)));
         CKB(kb_attend_fwd<T>(IP, QP, wlin_eff, P + lin.b, IF, att, IE, B, O, H, Dp, drop_for(cfg.attn_dropout, 1), s));
-        CKB(gemm_fwd(q, H, B, qproj, QR, H, EPI_RELU, 0, nd, 0, s));
-        CKB(gemm_fwd(IE, Dp, B, iproj, IR, H, EPI_RELU, 0, nd, 0, s));
+        if constexpr (MIXED) CKB(k_sf_image(IE, Dp, IEb, Dp, B, Dp, s));
+        CKB(gemm_fwd(q, H, B, qproj, QR, H, EPI_RELU, 0, nd, 0, s, cb(QRb)));
+        CKB(gemm_fwd(IE, Dp, B, iproj, IR, H, EPI_RELU, 0, nd, 0, s, cb(IRb)));
         CKB(kb_mul_fwd<T>(QR, IR, J, (size_t)B * H, s));
-        CKB(gemm_fwd(J, H, B, c0, C1, 2 * H, EPI_RELU_DROP, 0, drop_raw(cfg.hidden_dropout), 2, s));
+        if constexpr (MIXED) CKB(k_sf_image(J, H, Jb, H, B, H, s));
+        CKB(gemm_fwd(J, H, B, c0, C1, 2 * H, EPI_RELU_DROP, 0, drop_raw(cfg.hidden_dropout), 2, s, cb(C1b)));
         if (LP) {       // the LDS-DMA kernels want N % 8 == 0: all op = round_up(NA, 64) columns (zero weight rows, zero-padded bias: exact zeros)
             GemmGroup g; ginit(g);
             GemmProblem& p = g.p[0];
@@ -316,12 +353,12 @@ public:
         float* dl32 = dwscr;
         CKB(k_bce_fwd_bwd(logits, NAp, target, ldt, loss_dev, dl32, NAp, B, NA, NAp, grad_scale, s, db_part));      // (db_part: B floats, free until the backward pass below)
         if (loss_out) CKB(rgqa_check_hip(hipMemcpyAsync(loss_out, loss_dev, sizeof(float), hipMemcpyDeviceToDevice, s), "loss copy"));
-        CKB(k_cast_pad<T>(dl32, NAp, dlogits, NAp, B, NAp, 1.0f, s));
+        CKB(k_cast_pad<TB>(dl32, NAp, dlogits, NAp, B, NAp, 1.0f, s));
         return backward_impl(accumulate, s);
     }
     int backward(const float* dl, int ldd, int accumulate, hipStream_t s) override {
         RGQA_REQUIRE(have_fwd && G != nullptr && dl != nullptr, "backward: no forward pass recorded / null argument");
-        CKB(k_cast_pad<T>(dl, ldd, dlogits, NAp, B, NA, 1.0f, s));
+        CKB(k_cast_pad<TB>(dl, ldd, dlogits, NAp, B, NA, 1.0f, s));
         return backward_impl(accumulate, s);
     }
     int backward_pooled(const float*, int, int, hipStream_t) override { rgqa_set_error("backward_pooled: not available for the BUTD engine"); return RGQA_ERR_ARG; }
@@ -340,7 +377,7 @@ public:
             GemmProblem& p = wg.p[wg.count++];
             memset(&p, 0, sizeof p);
             const int r0 = i * kc, n = (i == S - 1) ? rows - r0 : kc;
-            p.A = (const T*)dy + (size_t)r0 * lddy; p.lda = lddy; p.B = (const T*)x + (size_t)r0 * ldx; p.ldb = ldx;
+            p.A = (const TB*)dy + (size_t)r0 * lddy; p.lda = lddy; p.B = (const TB*)x + (size_t)r0 * ldx; p.ldb = ldx;
             p.C = direct ? G + l.v : dwp(l) + (size_t)i * l.out * l.kp; p.ldc = direct ? l.in : l.kp;
             p.M = l.out; p.N = direct ? l.in : l.kp; p.K = n; p.epi = EPI_BIAS;
             p.colsum_out = S > 1 ? bpp(l) + (size_t)i * l.out : G + l.b;
@@ -350,23 +387,23 @@ public:
 
     int backward_impl(int accumulate, hipStream_t s) {
         const DropCfg nd = make_drop(0.f, 0, 0);
-        const T* q = Hall + (size_t)L * B * H;
+        const TB* q = Hb + (size_t)L * B * H;
         if (!accumulate) CKB(rgqa_check_hip(hipMemsetAsync(G + emb, 0, sizeof(float) * (size_t)cfg.vocab_size * E, s), "zero embedding grad"));
         wg_collect = LP && !accumulate;
         memset(&wg, 0, sizeof wg); wg.drop = make_drop(0.f, 0, 0);
         // classifier
-        CKB(wgrad(dlogits, NAp, C1, 2 * H, B, c3, accumulate, s));
-        CKB(gemm_dgrad(dlogits, NAp, B, c3, dC1, 2 * H, EPI_DRELU_DROP, C1, 2 * H, drop_raw(cfg.hidden_dropout), s));
-        CKB(wgrad(dC1, 2 * H, J, H, B, c0, accumulate, s));
+        CKB(wgrad(dlogits, NAp, C1b, 2 * H, B, c3, accumulate, s));
+        CKB(gemm_dgrad(dlogits, NAp, B, c3, dC1, 2 * H, EPI_DRELU_DROP, C1b, 2 * H, drop_raw(cfg.hidden_dropout), s));
+        CKB(wgrad(dC1, 2 * H, Jb, H, B, c0, accumulate, s));
         CKB(gemm_dgrad(dC1, 2 * H, B, c0, dJ, H, EPI_BIAS, nullptr, 0, nd, s));
-        CKB(kb_mul_relu_bwd<T>(dJ, QR, IR, dQR, dIR, (size_t)B * H, s));
+        CKB(kb_mul_relu_bwd<TB>(dJ, QRb, IRb, dQR, dIR, (size_t)B * H, s));
         // projections
         CKB(wgrad(dQR, H, q, H, B, qproj, accumulate, s));
         CKB(gemm_dgrad(dQR, H, B, qproj, dq, H, EPI_BIAS, nullptr, 0, nd, s));
-        CKB(wgrad(dIR, H, IE, Dp, B, iproj, accumulate, s));
+        CKB(wgrad(dIR, H, IEb, Dp, B, iproj, accumulate, s));
         CKB(gemm_dgrad(dIR, H, B, iproj, dIE, Dp, EPI_BIAS, nullptr, 0, nd, s));
         // attention over regions
-        CKB(kb_attend_bwd<T>(dIE, IF, att, IP, QP, wlin_eff, dIP, dQP, dw_part, db_part, B, O, H, Dp, drop_for(cfg.attn_dropout, 1), s));
+        CKB(kb_attend_bwd<TB>(dIE, IFb, att, IPb, QPb, wlin_eff, dIP, dQP, dw_part, db_part, B, O, H, Dp, drop_for(cfg.attn_dropout, 1), s));
         if (wg_collect) {
             CKB(k_colsum<float>(dw_part, H, partial, dwp(lin), 0, B, H, s));          // dW of att.linear [1, H]: folded through its weight norm with the others
         } else {
@@ -375,29 +412,29 @@ public:
         }
         hipLaunchKernelGGL(butd_sum_small_kernel, dim3(1), dim3(256), 0, s, db_part, B, G + lin.b, accumulate);
         RGQA_LAUNCH_CHECK("butd_sum_small_kernel");
-        CKB(wgrad(dIP, H, IF, Dp, B * O, ip, accumulate, s));
+        CKB(wgrad(dIP, H, IFb, Dp, B * O, ip, accumulate, s));
         CKB(wgrad(dQP, H, q, H, B, qp, accumulate, s));
         CKB(gemm_dgrad(dQP, H, B, qp, dHa, H, EPI_ADD, dq, H, nd, s));          // dHa = d q_enc = both question paths
         // GRU, back through time
-        T* dh = dHa; T* dhn = dHb;
+        TB* dh = dHa; TB* dhn = dHb;
         bool gru_host = true;
-        if constexpr (LP && !X3) {
-            if (gru_persist()) {
-                CKB(k_gru_bwd_persist(dHa, Hall, Rg, Zg, Ng, GHN, dGI, (long)L * 3 * H, dGH, efftp(whh), whh.op, B, L, H, gru_cnt, s));
+        if constexpr (std::is_same<TB, bf16_t>::value) {
+            if (gru_persist_bwd()) {
+                CKB(k_gru_bwd_persist(dHa, Hb, Rg, Zg, Ng, GHN, dGI, (long)L * 3 * H, dGH, efftp(whh), whh.op, B, L, H, gru_cnt, s));
                 gru_host = false;
             }
         }
         if (gru_host)
         for (int t = L - 1; t >= 0; --t) {
-            const T* hp = Hall + (size_t)t * B * H;
-            T* dgh_t = dGH + (size_t)t * B * 3 * H;
-            CKB(kb_gru_bwd<T>(dh, hp, Rg + (size_t)t * B * H, Zg + (size_t)t * B * H, Ng + (size_t)t * B * H, GHN + (size_t)t * B * H,
+            const TB* hp = Hb + (size_t)t * B * H;
+            TB* dgh_t = dGH + (size_t)t * B * 3 * H;
+            CKB(kb_gru_bwd<TB>(dh, hp, Rg + (size_t)t * B * H, Zg + (size_t)t * B * H, Ng + (size_t)t * B * H, GHN + (size_t)t * B * H,
                               dGI + (size_t)t * 3 * H, (long)L * 3 * H, dgh_t, tmpH, B, H, s));
             CKB(gemm_dgrad(dgh_t, 3 * H, B, whh, dhn, H, EPI_ADD, tmpH, H, nd, s));
-            T* x = dh; dh = dhn; dhn = x;
+            TB* x = dh; dh = dhn; dhn = x;
         }
-        CKB(wgrad(dGH, 3 * H, Hall, H, L * B, whh, accumulate, s));
-        CKB(wgrad(dGI, 3 * H, X, Ep, B * L, wih, accumulate, s));
+        CKB(wgrad(dGH, 3 * H, Hb, H, L * B, whh, accumulate, s));
+        CKB(wgrad(dGI, 3 * H, Xb, Ep, B * L, wih, accumulate, s));
         CKB(gemm_dgrad(dGI, 3 * H, B * L, wih, dX, Ep, EPI_BIAS, nullptr, 0, nd, s));
         // dense gradient of the word table (nn.Embedding(padding_idx = ntoken): that row gets none, butd.py:36), every table row summed by one workgroup
         // in a fixed order (csrc/embed.hip; until round 6 a float-atomic scatter-add: the last bits changed from run to run)
@@ -405,7 +442,7 @@ public:
         {
             const size_t need = (size_t)64 * cdiv(B * L, 256) * E;      // the hot words' partial sums
             RGQA_REQUIRE(need <= partial_floats, "embedding gradients: %zu floats of scratch needed", need);
-            CKB(k_embed_table_grads<T>(dX, Ep, emb_keys, nullptr, nullptr, B * L, G + emb, nullptr, nullptr, E, 0, 0, cfg.vocab_size - 1, 0, accumulate,
+            CKB(k_embed_table_grads<TB>(dX, Ep, emb_keys, nullptr, nullptr, B * L, G + emb, nullptr, nullptr, E, 0, 0, cfg.vocab_size - 1, 0, accumulate,
                                        emb_keys + (((size_t)B * L + 3) & ~(size_t)3), partial, need, s));
         }
         if (wg_collect) {
@@ -442,5 +479,6 @@ public:
 EngineBase* make_butd_engine(const rgqa_config& cfg) {
     if (cfg.precision == RGQA_PRECISION_BF16) return new ButdEngine<bf16_t>(cfg);
     if (cfg.precision == RGQA_PRECISION_BF16X3) return new ButdEngine<sf32>(cfg);
+    if (cfg.precision == RGQA_PRECISION_BF16X3_FWD) return new ButdEngine<sf32, true>(cfg);
     return new ButdEngine<float>(cfg);
 }

@@ -506,6 +506,169 @@ __global__ __launch_bounds__(512) void gru_bwd_persist32_kernel(const GruBwdArgs
     }
 }
 
+// ---------------------------------------------------------------------------------------------------------------- split f32 (bf16x3_fwd precision)
+// The forward recurrence of the mixed precision (split-f32 forward, bf16 backward): the 32-unit slice and 32-sample row group of the form above, W_hh
+// and h_{t-1} held as hi + lo bf16 pairs (common.h, sf32) and every product formed as hi*hi + hi*lo + lo*hi on the bf16 matrix pipe, f32 accumulate.
+// The slice's weights are twice the bytes (192 KB hi + 192 KB lo): neither half fits the LDS beside anything else, and 8 waves (two per SIMD, 256
+// registers each) cannot hold 96 + 96 of them next to their operands.  So 4 waves, one per SIMD, each a quarter of the contraction (8 K-steps of 32)
+// for the three gates x two unit tiles:
+//   registers: the 48 hi fragments (192) and the lo fragments of gate r (64); the operand ONE sample tile at a time (8 lines of [32 hi | 32 lo]: 64)
+//   LDS:       the lo fragments of gates z and n (4 waves x 32 KB, read back as conflict-free b128 per lane), and the partial sums of one sample tile
+//              (4 waves x 6 tiles x 1 KB): folded in wave order (deterministic) by the two waves that finish that tile, before the next tile's go in
+//   (all 384 weight registers in the waves spilled 227 registers to scratch; with gate n's lo in LDS still 117)
+//   resources: 256 VGPRs + 136 AGPRs, no scratch, 155,664 bytes of LDS (hipcc -O3 -Rpass-analysis=kernel-resource-usage, gfx950): one workgroup per CU
+// Wave w finishes the gates of sample tile w & 1, unit tile w >> 1, a lane owning the same (sample, 4 units) at every step.  h_t is published as split
+// f32 (an 8-byte sc1 store of its 4 hi parts and one of its 4 lo parts; the hand-off of the forms above, unchanged) and its bf16 image - the hi parts -
+// goes to the backward's copy of Hall behind the signal; the saved gates are bf16 (read by the bf16 backward only).
+struct GruFwdX3Args {
+    const sf32* GI; long ldgi;                // [B, L, 3H] input projections incl. b_ih, split f32; row stride of a sample (elements)
+    const sf32* W; int ldw;                   // effective W_hh [3H, ldw], split f32
+    const float* bhh;                         // [3H]
+    sf32* Hall;                               // [(L + 1), B, H] split f32; Hall[0] = 0 (set by the caller)
+    bf16_t* Himg;                             // [(L + 1), B, H] bf16 image of Hall (Himg[0] = 0 set by the caller)
+    bf16_t *Rg, *Zg, *Ng, *GHN;               // [L, B, H] saved for the backward pass
+    int B, L;
+    int* cnt;                                 // [row groups][L + 1], zeroed
+    int* err;
+};
+
+template <int H, int GR>
+__global__ __launch_bounds__(256) void gru_fwd_persist_x3_kernel(const GruFwdX3Args a) {
+    constexpr int KSW = H / 32 / 4, CS = H / 32;                  // K-steps of 32 per wave; slices per row group
+    constexpr int WLO_OFF = 4 * 6 * 64 * 16, BAD_OFF = WLO_OFF + 4 * (3 - GR) * 2 * KSW * 1024;
+    extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
+    f32x4* xch = reinterpret_cast<f32x4*>(lds);                   // [4 waves][6 tiles: (gate, u)][64 lanes], one sample tile at a time
+    int* s_bad = reinterpret_cast<int*>(lds + BAD_OFF);           // (between them: the lo fragments of gates >= GR, [wave][gate][u][K-step][64 lanes])
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int fr = lane & 15, fq = lane >> 4;
+    const int cs = blockIdx.x % CS, rg = blockIdx.x / CS;
+    const int B = a.B, L = a.L;
+    const int kw0 = wave * KSW;
+    if (tid == 0) *s_bad = 0;
+    // this wave's weight fragments: rows {r, z, n} x 2 unit tiles of W_hh, its K range; K-step k of row n is the 128-byte line [32 hi | 32 lo]
+    bf16x8 whi[3][2][KSW], wlo[GR > 0 ? GR : 1][2][KSW];
+#pragma unroll
+    for (int g = 0; g < 3; ++g)
+#pragma unroll
+        for (int u = 0; u < 2; ++u)
+#pragma unroll
+            for (int ks = 0; ks < KSW; ++ks) {
+                const unsigned char* p = reinterpret_cast<const unsigned char*>(a.W + (size_t)(g * H + cs * 32 + u * 16 + fr) * a.ldw + (kw0 + ks) * 32) + fq * 16;
+                whi[g][u][ks] = *reinterpret_cast<const bf16x8*>(p);
+                if (g < GR) wlo[g][u][ks] = *reinterpret_cast<const bf16x8*>(p + 64);
+                else *reinterpret_cast<bf16x8*>(lds + WLO_OFF + (((wave * (3 - GR) + g - GR) * 2 + u) * KSW + ks) * 1024 + lane * 16) = *reinterpret_cast<const bf16x8*>(p + 64);
+            }
+    const int gm = wave & 1, gu = wave >> 1;
+    const int row = rg * 32 + gm * 16 + fr;
+    const bool live = row < B;
+    const int rowc = row < B ? row : B - 1;
+    const int u0 = cs * 32 + gu * 16 + fq * 4;                    // this lane's 4 hidden units: one 8-byte run of hi parts, one of lo parts
+    float bh[3][4];
+#pragma unroll
+    for (int g = 0; g < 3; ++g)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) bh[g][j] = a.bhh[g * H + u0 + j];
+    float hown[4] = {0.f, 0.f, 0.f, 0.f};
+    const auto rs_h = __builtin_amdgcn_make_buffer_rsrc(a.Hall, 0, (int)((size_t)(L + 1) * B * H * 4), 0x00020000);
+    int* cnt = a.cnt + rg * (L + 1);
+    int lrow[2];                                                   // the operand rows of this lane (clamped: the result of a row >= B is dropped)
+#pragma unroll
+    for (int m = 0; m < 2; ++m) { const int r = rg * 32 + m * 16 + fr; lrow[m] = r < B ? r : B - 1; }
+    const unsigned hown_off = (unsigned)(cs * 128 + (gu * 16 + fq * 4) * 2);      // byte offset of the own hi parts inside a row of Hall
+    bf16x4 rr, zz, nn, gg;
+    __syncthreads();
+    for (int t = 0; t < L; ++t) {
+        float gi[3][4];
+#pragma unroll
+        for (int g = 0; g < 3; ++g) load4(a.GI + (size_t)rowc * a.ldgi + (size_t)t * 3 * H + g * H + u0, gi[g]);
+        if (t > 0) {
+            if (live) {          // what the backward pass needs of step t - 1: behind that step's signal
+                const size_t o = ((size_t)(t - 1) * B + row) * H + u0;
+                *reinterpret_cast<bf16x4*>(a.Rg + o) = rr; *reinterpret_cast<bf16x4*>(a.Zg + o) = zz;
+                *reinterpret_cast<bf16x4*>(a.Ng + o) = nn; *reinterpret_cast<bf16x4*>(a.GHN + o) = gg;
+            }
+            if (tid == 0 && !gru_wait(cnt + t, CS, a.err)) *s_bad = 1;
+            __syncthreads();
+        }
+        float gh[3][4];
+#pragma unroll
+        for (int m = 0; m < 2; ++m) {
+            bf16x8 ahi[KSW], alo[KSW];
+            const unsigned base = (unsigned)(((size_t)t * B + lrow[m]) * H * 4) + kw0 * 128 + fq * 16;
+#pragma unroll
+            for (int ks = 0; ks < KSW; ++ks) {
+                const auto vh = __builtin_amdgcn_raw_buffer_load_b128(rs_h, base + ks * 128, 0, 16);        // aux 16 = sc1
+                const auto vl = __builtin_amdgcn_raw_buffer_load_b128(rs_h, base + ks * 128 + 64, 0, 16);
+                ahi[ks] = *reinterpret_cast<const bf16x8*>(&vh);
+                alo[ks] = *reinterpret_cast<const bf16x8*>(&vl);
+            }
+            __builtin_amdgcn_sched_barrier(0);   // the tile's operand loads are all in flight before the first MFMA waits for one
+#pragma unroll
+            for (int g = 0; g < 3; ++g)
+#pragma unroll
+                for (int u = 0; u < 2; ++u) {
+                    f32x4 acc = (f32x4){0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+                    for (int ks = 0; ks < KSW; ++ks) {
+                        acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(whi[g][u][ks], ahi[ks], acc, 0, 0, 0);
+                        acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(whi[g][u][ks], alo[ks], acc, 0, 0, 0);
+                        const bf16x8 wl = g < GR ? wlo[g][u][ks] : *reinterpret_cast<const bf16x8*>(lds + WLO_OFF + (((wave * (3 - GR) + g - GR) * 2 + u) * KSW + ks) * 1024 + lane * 16);
+                        acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wl, ahi[ks], acc, 0, 0, 0);
+                    }
+                    xch[(wave * 6 + g * 2 + u) * 64 + lane] = acc;
+                }
+            __syncthreads();
+            if (gm == m) {                       // the two waves of this sample tile fold the four partial sums, in wave order
+#pragma unroll
+                for (int g = 0; g < 3; ++g) {
+                    f32x4 sum = xch[(g * 2 + gu) * 64 + lane];
+#pragma unroll
+                    for (int p = 1; p < 4; ++p) sum += xch[(p * 6 + g * 2 + gu) * 64 + lane];
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) gh[g][j] = sum[j];
+                }
+            }
+            if (m == 0) __syncthreads();         // before the second tile's partial sums overwrite the first's
+        }
+        bf16x4 hh, hl;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const float r = sigm_f(gi[0][j] + gh[0][j] + bh[0][j]);
+            const float z = sigm_f(gi[1][j] + gh[1][j] + bh[1][j]);
+            const float gn = gh[2][j] + bh[2][j];
+            const float n = tanhf(gi[2][j] + r * gn);
+            const float h = (1.f - z) * n + z * hown[j];
+            bf16_t x, y; sf_split(h, x, y);
+            hh[j] = x; hl[j] = y; rr[j] = (bf16_t)r; zz[j] = (bf16_t)z; nn[j] = (bf16_t)n; gg[j] = (bf16_t)gn;
+            hown[j] = (float)x + (float)y;                           // what every other slice reads back
+        }
+        if (live) {
+            typedef __attribute__((ext_vector_type(2))) unsigned u2;
+            const unsigned ho = (unsigned)(((size_t)(t + 1) * B + row) * H * 4) + hown_off;
+            __builtin_amdgcn_raw_buffer_store_b64(*reinterpret_cast<const u2*>(&hh), rs_h, ho, 0, 16);            // write-through
+            __builtin_amdgcn_raw_buffer_store_b64(*reinterpret_cast<const u2*>(&hl), rs_h, ho + 64, 0, 16);
+        }
+        if (t + 1 < L) {
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");         // every storing wave
+            __syncthreads();
+            if (tid == 0) __hip_atomic_fetch_add(cnt + t + 1, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+        if (live) *reinterpret_cast<bf16x4*>(a.Himg + ((size_t)(t + 1) * B + row) * H + u0) = hh;      // the backward's image: nobody's hand-off
+    }
+    __syncthreads();
+    if (live) {
+        const size_t o = ((size_t)(L - 1) * B + row) * H + u0;
+        *reinterpret_cast<bf16x4*>(a.Rg + o) = rr; *reinterpret_cast<bf16x4*>(a.Zg + o) = zz;
+        *reinterpret_cast<bf16x4*>(a.Ng + o) = nn; *reinterpret_cast<bf16x4*>(a.GHN + o) = gg;
+        if (*s_bad) {            // a poll gave up: the final state of this slice says so (hi and lo parts, and the image)
+            const unsigned long long q = 0x7FC07FC07FC07FC0ull;      // four bf16 NaNs
+            unsigned char* hp = reinterpret_cast<unsigned char*>(a.Hall + ((size_t)L * B + row) * H) + hown_off;
+            *reinterpret_cast<unsigned long long*>(hp) = q; *reinterpret_cast<unsigned long long*>(hp + 64) = q;
+            *reinterpret_cast<unsigned long long*>(a.Himg + ((size_t)L * B + row) * H + u0) = q;
+        }
+    }
+}
+
 // ---------------------------------------------------------------------------------------------------------------- launchers
 int g_rgqa_butd_gru_persist = 3;      // rgqa_debug_set key 18: 0 = the host-driven recurrence (one GEMM + one gate kernel per token); 1 = persistent, 64-sample row groups x
                                       // 16-unit slices, W_hh slice in LDS, 4 waves; 2 = the same with 8 waves (the contraction split over wave pairs); 3 (default) = persistent,
@@ -566,5 +729,38 @@ int k_gru_bwd_persist(const bf16_t* dH, const bf16_t* Hall, const bf16_t* Rg, co
     else if (g_rgqa_butd_gru_persist != 2) hipLaunchKernelGGL((gru_bwd_persist_kernel<HH, 1>), dim3(RG * (HH / 16)), dim3(256), LDS_BYTES, s, a);
     else hipLaunchKernelGGL((gru_bwd_persist_kernel<HH, 2>), dim3(RG * (HH / 16)), dim3(512), LDS_BYTES, s, a);
     RGQA_LAUNCH_CHECK("gru_bwd_persist_kernel");
+    return RGQA_OK;
+}
+
+// split-f32 forward (gru_fwd_persist_x3_kernel<1024, X3_GR>): 32-sample row groups x 32 slices whatever the (non-zero) value of key 18; 256 threads,
+// 152 KB of LDS.  Applies when every workgroup is resident at once: the grid fits the CUs and the occupancy API grants one block per CU.
+static constexpr int X3_GR = 1, X3_LDS = 4 * 6 * 64 * 16 + 4 * (3 - X3_GR) * 2 * 8 * 1024 + 16;
+static int x3_blocks_per_cu() {
+    static int per_dev[64];
+    static bool known[64] = {};
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess) return 0;
+    if (!known[dev & 63]) {
+        int n = 0;
+        if (hipFuncSetAttribute(reinterpret_cast<const void*>(&gru_fwd_persist_x3_kernel<1024, X3_GR>), hipFuncAttributeMaxDynamicSharedMemorySize, X3_LDS) != hipSuccess ||
+            hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, reinterpret_cast<const void*>(&gru_fwd_persist_x3_kernel<1024, X3_GR>), 256, X3_LDS) != hipSuccess) n = 0;
+        per_dev[dev & 63] = n; known[dev & 63] = true;
+    }
+    return per_dev[dev & 63];
+}
+bool gru_persist_x3_ok(int B, int H) {
+    return g_rgqa_butd_gru_persist != 0 && H == 1024 && B >= 1 && B <= 256 && gru_rgm(B) * (H / 32) <= rgqa_num_cus() && x3_blocks_per_cu() >= 1;
+}
+int k_gru_fwd_persist_x3(const sf32* GI, long ldgi, const sf32* W, int ldw, const float* bhh, sf32* Hall, bf16_t* Himg, bf16_t* Rg, bf16_t* Zg, bf16_t* Ng,
+                         bf16_t* GHN, int B, int L, int H, int* counters, hipStream_t s) {
+    RGQA_REQUIRE(gru_persist_x3_ok(B, H), "gru_fwd_persist_x3: B=%d H=%d not covered (grid / residency)", B, H);
+    RGQA_REQUIRE(ldw % 32 == 0 && ldw >= H && ldgi % 32 == 0, "gru_fwd_persist_x3: ldw=%d ldgi=%ld must be whole split-f32 lines", ldw, ldgi);
+    RGQA_REQUIRE((size_t)(L + 1) * B * H * 4 < ((size_t)1 << 31), "gru_fwd_persist_x3: L=%d too long for one buffer resource", L);
+    constexpr int HH = 1024;
+    const int RGM = gru_rgm(B);
+    RGQA_HIP(hipMemsetAsync(counters, 0, sizeof(int) * (size_t)RGM * (2 * L + 1), s));
+    GruFwdX3Args a{GI, ldgi, W, ldw, bhh, Hall, Himg, Rg, Zg, Ng, GHN, B, L, counters, counters + (size_t)RGM * (2 * L + 1)};
+    hipLaunchKernelGGL((gru_fwd_persist_x3_kernel<HH, X3_GR>), dim3(RGM * (HH / 32)), dim3(256), X3_LDS, s, a);
+    RGQA_LAUNCH_CHECK("gru_fwd_persist_x3_kernel");
     return RGQA_OK;
 }

@@ -1,7 +1,7 @@
 // Kernels of the BUTD GQA path (reference src/butd/butd.py; BASELINE config 5): GloVe embedding
 // gather, GRU gates, product-fusion attention over the 36 regions (softmax over regions, weighted feature sum),
 // weight-norm (scalar g) weight preparation / gradient, and small elementwise helpers.  The projections themselves run
-// on the GEMM kernels shared with the LXMERT path.  All HBM-bound; T = float (parity) or bf16.
+// on the GEMM kernels shared with the LXMERT path.  All HBM-bound; T = float (parity), bf16 or sf32 (split f32).
 #include <type_traits>
 #include "kernels.h"
 #include "butd.h"
@@ -24,9 +24,11 @@ __global__ void butd_embed_bwd_kernel(const int64_t* __restrict__ toks, const T*
 // ---------------------------------------------------------------- GRU gates (gate order r, z, n as torch.nn.GRU)
 __device__ __forceinline__ float sigm(float x) { return 1.f / (1.f + __expf(-x)); }
 
-template <typename T>
+// TS: type of the saved gates; himg (bf16x3_fwd, else null): the bf16 image of h_t - the hi part of its split-f32 value
+template <typename T, typename TS = T>
 __global__ void gru_gate_fwd_kernel(const T* __restrict__ gi, long ldgi, const T* __restrict__ gh, const T* __restrict__ hprev,
-                                    T* __restrict__ hnew, T* __restrict__ rs, T* __restrict__ zs, T* __restrict__ ns, T* __restrict__ ghn, int B, int H) {
+                                    T* __restrict__ hnew, TS* __restrict__ rs, TS* __restrict__ zs, TS* __restrict__ ns, TS* __restrict__ ghn, int B, int H,
+                                    bf16_t* __restrict__ himg) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= B * H) return;
     const int b = i / H, h = i % H;
@@ -37,7 +39,9 @@ __global__ void gru_gate_fwd_kernel(const T* __restrict__ gi, long ldgi, const T
     const float gn = ld_elem(ghb + (2 * H + h));
     const float n = tanhf(ld_elem(gib + (2 * H + h)) + r * gn);
     const float hp = ld_elem(hprev + (i));
-    st_elem(hnew + (i), (1.f - z) * n + z * hp);
+    const float hv = (1.f - z) * n + z * hp;
+    st_elem(hnew + (i), hv);
+    if (himg != nullptr) himg[i] = (bf16_t)hv;
     st_elem(rs + (i), r); st_elem(zs + (i), z); st_elem(ns + (i), n); st_elem(ghn + (i), gn);
 }
 // given dh (gradient w.r.t. h_t): dgi / dgh for this step and the direct part of dh_{t-1} (= dh * z)
@@ -60,14 +64,16 @@ __global__ void gru_gate_bwd_kernel(const T* __restrict__ dh, const T* __restric
 }
 
 // ---------------------------------------------------------------- image features = cat(feat, pos), padded to a multiple of 8 columns
+// img (bf16x3_fwd, else null): the bf16 image of the split-f32 result
 template <typename T>
-__global__ void concat_cast_kernel(const float* __restrict__ feat, const float* __restrict__ pos, T* __restrict__ out, int F, int Pd, int Dp) {
+__global__ void concat_cast_kernel(const float* __restrict__ feat, const float* __restrict__ pos, T* __restrict__ out, int F, int Pd, int Dp, bf16_t* __restrict__ img) {
     const int row = blockIdx.x;
     for (int c = threadIdx.x; c < Dp; c += blockDim.x) {
         float v = 0.f;
         if (c < F) v = feat[(size_t)row * F + c];
         else if (c < F + Pd) v = pos[(size_t)row * Pd + (c - F)];
         st_elem(out + ((size_t)row * Dp + c), v);
+        if (img != nullptr) img[(size_t)row * Dp + c] = (bf16_t)v;
     }
 }
 
@@ -402,7 +408,7 @@ __device__ __forceinline__ float wn_fold(const float* partial, const WnDesc& d) 
     return s;
 }
 // effective weight [op, kp] (zero padded past `in`; rows past `out` are the caller's zeros) and its transpose [kp, op]; 32 x 32 tiles
-template <typename T>
+template <typename T, typename TT = T>      // TT: element type of the transposed copy (bf16x3_fwd: split-f32 eff, bf16 efft)
 __global__ __launch_bounds__(256) void wn_eff_group_kernel(const WnDesc* __restrict__ descs, int nd, const float* __restrict__ partial) {
     __shared__ float tile[32][33];
     const int l = wn_find(descs, nd, blockIdx.x, &WnDesc::tile0);
@@ -416,7 +422,7 @@ __global__ __launch_bounds__(256) void wn_eff_group_kernel(const WnDesc* __restr
     const int lt = blockIdx.x - d.tile0;
     const int n0 = (lt / d.tiles_x) * 32, k0 = (lt % d.tiles_x) * 32, tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
     T* w = reinterpret_cast<T*>(d.eff);
-    T* wt = reinterpret_cast<T*>(d.efft);
+    TT* wt = reinterpret_cast<TT*>(d.efft);
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
         const int n = n0 + ty + r * 8, k = k0 + tx;
@@ -472,11 +478,12 @@ __global__ __launch_bounds__(256) void wn_bwd_group_kernel(const WnDesc* __restr
     if (blockIdx.x == d.blk0 && threadIdx.x == 0) d.dgp[0] = dot / nrm;
 }
 
-int kb_wn_forward_group(const WnDesc* descs_dev, int nd, int total_blocks, int total_tiles, float* partial, int elem /* 0 f32, 1 bf16, 2 split f32 */, hipStream_t s) {
+int kb_wn_forward_group(const WnDesc* descs_dev, int nd, int total_blocks, int total_tiles, float* partial, int elem /* 0 f32, 1 bf16, 2 split f32, 3 split-f32 eff + bf16 efft */, hipStream_t s) {
     hipLaunchKernelGGL(wn_partials_group_kernel<0>, dim3(total_blocks), dim3(256), 0, s, descs_dev, nd, partial);
     RGQA_LAUNCH_CHECK("wn_partials_group_kernel");
     if (elem == 1) hipLaunchKernelGGL(wn_eff_group_kernel<bf16_t>, dim3(total_tiles), dim3(256), 0, s, descs_dev, nd, partial);
     else if (elem == 2) hipLaunchKernelGGL(wn_eff_group_kernel<sf32>, dim3(total_tiles), dim3(256), 0, s, descs_dev, nd, partial);
+    else if (elem == 3) hipLaunchKernelGGL((wn_eff_group_kernel<sf32, bf16_t>), dim3(total_tiles), dim3(256), 0, s, descs_dev, nd, partial);
     else hipLaunchKernelGGL(wn_eff_group_kernel<float>, dim3(total_tiles), dim3(256), 0, s, descs_dev, nd, partial);
     RGQA_LAUNCH_CHECK("wn_eff_group_kernel");
     return RGQA_OK;
@@ -501,7 +508,12 @@ template <typename T> int kb_embed_bwd(const int64_t* toks, const T* dx, float* 
     RGQA_LAUNCH_CHECK("butd_embed_bwd_kernel"); return RGQA_OK;
 }
 template <typename T> int kb_gru_fwd(const T* gi, long ldgi, const T* gh, const T* hprev, T* hnew, T* rs, T* zs, T* ns, T* ghn, int B, int H, hipStream_t s) {
-    hipLaunchKernelGGL(gru_gate_fwd_kernel<T>, dim3(cdiv((long)B * H, 256)), dim3(256), 0, s, gi, ldgi, gh, hprev, hnew, rs, zs, ns, ghn, B, H);
+    hipLaunchKernelGGL(gru_gate_fwd_kernel<T>, dim3(cdiv((long)B * H, 256)), dim3(256), 0, s, gi, ldgi, gh, hprev, hnew, rs, zs, ns, ghn, B, H, (bf16_t*)nullptr);
+    RGQA_LAUNCH_CHECK("gru_gate_fwd_kernel"); return RGQA_OK;
+}
+int kb_gru_fwd_x3img(const sf32* gi, long ldgi, const sf32* gh, const sf32* hprev, sf32* hnew, bf16_t* himg, bf16_t* rs, bf16_t* zs, bf16_t* ns, bf16_t* ghn,
+                     int B, int H, hipStream_t s) {
+    hipLaunchKernelGGL((gru_gate_fwd_kernel<sf32, bf16_t>), dim3(cdiv((long)B * H, 256)), dim3(256), 0, s, gi, ldgi, gh, hprev, hnew, rs, zs, ns, ghn, B, H, himg);
     RGQA_LAUNCH_CHECK("gru_gate_fwd_kernel"); return RGQA_OK;
 }
 template <typename T> int kb_gru_bwd(const T* dh, const T* hprev, const T* rs, const T* zs, const T* ns, const T* ghn, T* dgi, long lddgi, T* dgh, T* dhprev, int B, int H, hipStream_t s) {
@@ -509,7 +521,11 @@ template <typename T> int kb_gru_bwd(const T* dh, const T* hprev, const T* rs, c
     RGQA_LAUNCH_CHECK("gru_gate_bwd_kernel"); return RGQA_OK;
 }
 template <typename T> int kb_concat(const float* feat, const float* pos, T* out, int rows, int F, int Pd, int Dp, hipStream_t s) {
-    hipLaunchKernelGGL(concat_cast_kernel<T>, dim3(rows), dim3(256), 0, s, feat, pos, out, F, Pd, Dp);
+    hipLaunchKernelGGL(concat_cast_kernel<T>, dim3(rows), dim3(256), 0, s, feat, pos, out, F, Pd, Dp, (bf16_t*)nullptr);
+    RGQA_LAUNCH_CHECK("concat_cast_kernel"); return RGQA_OK;
+}
+int kb_concat_x3img(const float* feat, const float* pos, sf32* out, bf16_t* img, int rows, int F, int Pd, int Dp, hipStream_t s) {
+    hipLaunchKernelGGL(concat_cast_kernel<sf32>, dim3(rows), dim3(256), 0, s, feat, pos, out, F, Pd, Dp, img);
     RGQA_LAUNCH_CHECK("concat_cast_kernel"); return RGQA_OK;
 }
 template <typename T> int kb_attend_fwd(const T* ip, const T* qp, const float* wlin, const float* blin, const T* imgf, float* att, T* img_enc, int B, int O, int H, int Dp, DropCfg drop, hipStream_t s) {
