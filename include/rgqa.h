@@ -156,7 +156,8 @@ int rgqa_engine_get_cross_attention(rgqa_engine* e, int layer, int direction, fl
 int rgqa_engine_set_lengths(rgqa_engine* e, const int32_t* lengths, int n);
 /* Input gradients for the FOLLOWING backward calls (the reference's ODIN scorer differentiates w.r.t. the RoI features and boxes,
  * tasks/gqa_odin.py:97-121): dfeats [B*O, feat_dim] f32, dboxes [B*O, pos_dim] f32 device buffers, either may be NULL (not computed,
- * the default). */
+ * the default).  Every backbone: LXMERT, BUTD (dboxes = the 4 box columns of cat(feat, pos)) and UNITER (dboxes = dL/dpos, pos_dim 7).
+ * Parameter gradients are bit-identical with and without the buffers. */
 int rgqa_engine_set_input_grads(rgqa_engine* e, float* dfeats, float* dboxes);
 /* Per-segment sum of squared gradients for clip_grad_norm_ (tasks/gqa_conf.py:201): slots (device, n >= rgqa_engine_num_grad_segments
  * floats, or null to switch off) receives, during every following backward call, sum(g^2) of gradient segment k as soon as that segment
@@ -300,6 +301,19 @@ int rgqa_host_gather_rows(const void* src, size_t row_bytes, size_t n_src_rows, 
 int rgqa_score_rows(const float* logits, int ld, int B, int NA, float temperature, int k, float* max_score,
                     int64_t* label, float* energy, float* topk_val, int64_t* topk_idx, float* topk_energy,
                     void* stream);
+
+/* The two steps the ODIN scorer adds (tasks/gqa_odin.py:101-121), for the logits of a forward pass whose backward then runs with
+ * rgqa_engine_set_input_grads buffers.
+ *   dlogits [B, ldd >= NAp >= NA] = d loss / d logits of loss = mean_b BCEWithLogits(logit[b, label[b]], y[b]), y[b] = (max_score[b] >= 0.5):
+ *   label / max_score are what rgqa_score_rows returned for the SAME logits and temperature (the reference's idx = argmax and
+ *   labels = preds >= 0.5 at that column; NOT logit >= 0 - at temperature 1e5 the f32 sigmoid of a small negative logit is exactly 0.5).
+ *   dlogits[b, label[b]] = (sigmoid(logit) - y) / B on the un-tempered logit; every other column up to NAp is an exact zero.
+ *   loss (1 float, or NULL) = that mean, folded in a fixed order. */
+int rgqa_odin_dlogits(const float* logits, int ld, const int64_t* label, const float* max_score, int B, int NA, int NAp,
+                      float* dlogits, int ldd, float* loss, void* stream);
+/* out[i] = x[i] - noise * (grad[i] >= 0 ? 1 : -1), i < n (gqa_odin.py:115-121; torch.ge: 0 and -0.0 step by -noise, NaN by +noise).
+ * out may alias x. */
+int rgqa_sign_step(const float* x, const float* grad, float noise, float* out, size_t n, void* stream);
 
 /* ---- stand-alone operators (unit parity tests; the engine calls the same kernels internally) ------------- */
 /* dtype of the stand-alone operators: 0 f32, 1 bf16, 2 split f32 (every activation / weight operand in the split layout, ld % 32 == 0).

@@ -29,6 +29,10 @@ template <typename T> int kb_concat(const float* feat, const float* pos, T* out,
 template <typename T> int kb_attend_fwd(const T* ip, const T* qp, const float* wlin, const float* blin, const T* imgf, float* att, T* img_enc, int B, int O, int H, int Dp, DropCfg drop, hipStream_t s);
 template <typename T> int kb_attend_bwd(const T* dimg, const T* imgf, const float* att, const T* ip, const T* qp, const float* wlin, T* dip, T* dqp, float* dw_part, float* db_part,
                                         int B, int O, int H, int Dp, DropCfg drop, hipStream_t s);
+// input gradients (ODIN): dfeats[row, :F] += att[row] * die[b, :F] on top of the dgrad GEMM's result; dboxes[row, j] = att[row] * die[b, F + j] +
+// sum_k dip[row, k] * w[k * wsk + j * wsj] (the Pd box columns of the image projection's effective weight); either output may be null
+template <typename T> int kb_input_grad_finish(const T* die, int Dp, const float* att, const T* dip, int H, const T* w, long wsk, long wsj, float* dfeats, float* dboxes,
+                                               int rows, int O, int F, int Pd, hipStream_t s);
 template <typename T> int kb_mul_fwd(const T* a, const T* b, T* out, size_t n, hipStream_t s);
 template <typename T> int kb_mul_relu_bwd(const T* dj, const T* a, const T* b, T* da, T* db, size_t n, hipStream_t s);
 // effective weight of a (weight-normed when g != null) linear: w [N, ldo] (+ transposed wt [K, ldt] when wt != null)

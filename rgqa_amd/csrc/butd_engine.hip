@@ -385,6 +385,38 @@ public:
         return RGQA_OK;
     }
 
+    // dL/dfeats [B*O, feat_dim], dL/dboxes [B*O, pos_dim] (f32, the caller's buffers) for the backward passes that follow; NULL: not computed
+    float* dfeats_out = nullptr; float* dboxes_out = nullptr;
+    int set_input_grads(float* dfeats, float* dboxes) override { dfeats_out = dfeats; dboxes_out = dboxes; return RGQA_OK; }
+    // IF = cat(feat, pos) feeds the image projection and the attended sum (butd.py:199, 207-208): dIF = att (x) dIE + dIP @ W_eff(att.image_proj).
+    // The feature columns of the second term are one dgrad GEMM straight into dfeats (no [B*O, Dp] staging buffer: the workspace does not grow);
+    // kb_input_grad_finish adds the first term and forms the box columns.  Reads dIE / dIP / att as the backward pass left them, writes nothing else.
+    int input_grads(hipStream_t s) {
+        const int F = cfg.feat_dim, Pd = cfg.pos_dim;
+        if (dfeats_out != nullptr) {
+            RGQA_REQUIRE(!LP || F % 8 == 0, "butd input gradients: feat_dim %d must be a multiple of 8", F);
+            // bf16: the f32-result LDS-DMA kernel takes problems of at most 512 rows (csrc/gemm_mfma256.hip), so the B*O rows go as 512-row slices,
+            // up to 12 problems per grouped launch; as ONE problem of 9216 rows the GEMM fell to the 128 x 128 register-staged kernel (127 us at B = 256)
+            const int M = B * O, slice = std::is_same<TB, bf16_t>::value ? 512 : M;
+            for (int r0 = 0; r0 < M;) {
+                GemmGroup g; ginit(g); g.count = 0;
+                while (r0 < M && g.count < GEMM_NT_MAX_PROBLEMS) {
+                    GemmProblem& p = g.p[g.count++];
+                    memset(&p, 0, sizeof p);
+                    const int rows = M - r0 < slice ? M - r0 : slice;
+                    p.A = dIP + (size_t)r0 * H; p.lda = H; p.C = dfeats_out + (size_t)r0 * F; p.ldc = F; p.M = rows; p.N = F; p.epi = EPI_BIAS;
+                    if (LP) { p.B = efftp(ip); p.ldb = ip.op; p.K = (int)rupb(ip.out, LDM) > ip.op ? ip.op : (int)rupb(ip.out, LDM); }
+                    else { p.B = effp(ip); p.ldb = ip.kp; p.K = ip.out; }
+                    r0 += rows;
+                }
+                if (LP) CKB(nt_gemm_b(g, 1, 1, s));
+                else CKB(launch_gemm_f32(g, 0, 1, s));
+            }
+        }
+        if constexpr (LP) return kb_input_grad_finish<TB>(dIE, Dp, att, dIP, H, efftp(ip) + (size_t)F * ip.op, 1, ip.op, dfeats_out, dboxes_out, B * O, O, F, Pd, s);
+        else return kb_input_grad_finish<TB>(dIE, Dp, att, dIP, H, (const TB*)effp(ip) + F, ip.kp, 1, dfeats_out, dboxes_out, B * O, O, F, Pd, s);
+    }
+
     int backward_impl(int accumulate, hipStream_t s) {
         const DropCfg nd = make_drop(0.f, 0, 0);
         const TB* q = Hb + (size_t)L * B * H;
@@ -413,6 +445,7 @@ public:
         hipLaunchKernelGGL(butd_sum_small_kernel, dim3(1), dim3(256), 0, s, db_part, B, G + lin.b, accumulate);
         RGQA_LAUNCH_CHECK("butd_sum_small_kernel");
         CKB(wgrad(dIP, H, IFb, Dp, B * O, ip, accumulate, s));
+        if (dfeats_out != nullptr || dboxes_out != nullptr) CKB(input_grads(s));
         CKB(wgrad(dQP, H, q, H, B, qp, accumulate, s));
         CKB(gemm_dgrad(dQP, H, B, qp, dHa, H, EPI_ADD, dq, H, nd, s));          // dHa = d q_enc = both question paths
         // GRU, back through time

@@ -274,6 +274,60 @@ __global__ __launch_bounds__(256) void butd_attend_bwd_bf16_kernel(const bf16_t*
     }
 }
 
+// ---------------------------------------------------------------- input gradients (ODIN: tasks/gqa_odin.py:97-121)
+// dIF[row, :] = att[row] * dIE[b, :] + dIP[row, :] @ W_eff(att.image_proj), IF = cat(feat, pos) (butd.py:199, 207-208).  The dgrad GEMM has
+// already written the second term of the F feature columns into dfeats; one workgroup per region row adds att (x) dIE to them (16-byte
+// accesses on dfeats) and forms the Pd box columns whole: dots of length H, no GEMM.  W(k, j) = w[k * wsk + j * wsj] is the effective weight
+// of output k, input column F + j (the engine's transposed copy: wsk = 1; the f32 engine's direct copy: wsj = 1).  Either output may be null.
+#define BUTD_MAXPOS 8
+template <typename T>
+__global__ __launch_bounds__(256) void butd_input_grad_finish_kernel(const T* __restrict__ die, int Dp, const float* __restrict__ att, const T* __restrict__ dip, int H,
+                                                                     const T* __restrict__ w, long wsk, long wsj, float* __restrict__ dfeats, float* __restrict__ dboxes,
+                                                                     int O, int F, int Pd) {
+    __shared__ float red[4][BUTD_MAXPOS];
+    const int row = blockIdx.x, b = row / O, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const float a = att[row];
+    const T* dieb = die + (size_t)b * Dp;
+    if (dfeats != nullptr) {
+        float* out = dfeats + (size_t)row * F;
+        for (int c = threadIdx.x * 4; c < F; c += 1024) {
+            float d[4], v[4];
+            load4(dieb + c, d);
+            load4(out + c, v);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) v[j] = fmaf(a, d[j], v[j]);
+            store4(out + c, v);
+        }
+    }
+    if (dboxes == nullptr) return;
+    float acc[BUTD_MAXPOS];
+#pragma unroll
+    for (int j = 0; j < BUTD_MAXPOS; ++j) acc[j] = 0.f;
+    const T* dipr = dip + (size_t)row * H;
+    for (int k0 = threadIdx.x * 4; k0 < H; k0 += 1024) {
+        float g[4];
+        load4(dipr + k0, g);
+#pragma unroll
+        for (int j = 0; j < BUTD_MAXPOS; ++j) if (j < Pd) {
+            float wv[4];
+            if (wsk == 1) load4(w + (size_t)j * wsj + k0, wv);
+            else for (int i = 0; i < 4; ++i) wv[i] = ld_elem(w + (size_t)(k0 + i) * wsk + (size_t)j * wsj);
+#pragma unroll
+            for (int i = 0; i < 4; ++i) acc[j] = fmaf(g[i], wv[i], acc[j]);
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < BUTD_MAXPOS; ++j) {
+        const float t = wave_sum(acc[j]);
+        if (lane == 0) red[wave][j] = t;
+    }
+    __syncthreads();
+    if (threadIdx.x < Pd) {
+        const int j = threadIdx.x;
+        dboxes[(size_t)row * Pd + j] = fmaf(a, ld_elem(dieb + F + j), red[0][j] + red[1][j] + red[2][j] + red[3][j]);
+    }
+}
+
 // ---------------------------------------------------------------- joint = q_repr * img_repr (both post-ReLU)
 template <typename T>
 __global__ void mul_fwd_kernel(const T* __restrict__ a, const T* __restrict__ b, T* __restrict__ out, size_t n) {
@@ -552,6 +606,14 @@ template <typename T> int kb_attend_bwd(const T* dimg, const T* imgf, const floa
     hipLaunchKernelGGL(butd_attend_bwd_kernel<T>, dim3(B), dim3(256), 0, s, dimg, imgf, att, ip, qp, wlin, dip, dqp, dw_part, db_part, O, H, Dp, drop);
     RGQA_LAUNCH_CHECK("butd_attend_bwd_kernel"); return RGQA_OK;
 }
+template <typename T> int kb_input_grad_finish(const T* die, int Dp, const float* att, const T* dip, int H, const T* w, long wsk, long wsj, float* dfeats, float* dboxes,
+                                               int rows, int O, int F, int Pd, hipStream_t s) {
+    RGQA_REQUIRE(Pd >= 0 && Pd <= BUTD_MAXPOS && F % 4 == 0 && H % 4 == 0 && F + Pd <= Dp && (wsk != 1 || wsj % 4 == 0),
+                 "butd input gradients: feat_dim %d / pos_dim %d / hidden %d unsupported", F, Pd, H);
+    if (rows <= 0 || (dfeats == nullptr && dboxes == nullptr)) return RGQA_OK;
+    hipLaunchKernelGGL(butd_input_grad_finish_kernel<T>, dim3(rows), dim3(256), 0, s, die, Dp, att, dip, H, w, wsk, wsj, dfeats, dboxes, O, F, Pd);
+    RGQA_LAUNCH_CHECK("butd_input_grad_finish_kernel"); return RGQA_OK;
+}
 template <typename T> int kb_mul_fwd(const T* a, const T* b, T* out, size_t n, hipStream_t s) {
     hipLaunchKernelGGL(mul_fwd_kernel<T>, GRID1(n), dim3(256), 0, s, a, b, out, n);
     RGQA_LAUNCH_CHECK("mul_fwd_kernel"); return RGQA_OK;
@@ -585,6 +647,7 @@ int kb_wn_bwd(const float* dw, int lddw, const float* v, const float* g, const f
     template int kb_concat<T>(const float*, const float*, T*, int, int, int, int, hipStream_t);                                          \
     template int kb_attend_fwd<T>(const T*, const T*, const float*, const float*, const T*, float*, T*, int, int, int, int, DropCfg, hipStream_t); \
     template int kb_attend_bwd<T>(const T*, const T*, const float*, const T*, const T*, const float*, T*, T*, float*, float*, int, int, int, int, DropCfg, hipStream_t); \
+    template int kb_input_grad_finish<T>(const T*, int, const float*, const T*, int, const T*, long, long, float*, float*, int, int, int, int, hipStream_t); \
     template int kb_mul_fwd<T>(const T*, const T*, T*, size_t, hipStream_t);                                                             \
     template int kb_mul_relu_bwd<T>(const T*, const T*, const T*, T*, T*, size_t, hipStream_t);                                          \
     template int kb_wn_eff<T>(const float*, const float*, const float*, T*, int, T*, int, int, int, hipStream_t);

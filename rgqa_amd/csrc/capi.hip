@@ -416,6 +416,11 @@ int rgqa_score_rows(const float* logits, int ld, int B, int NA, float temperatur
                     float* topk_val, int64_t* topk_idx, float* topk_energy, void* stream) {
     return k_score_rows(logits, ld, B, NA, temperature, k, max_score, label, energy, topk_val, topk_idx, topk_energy, S(stream));
 }
+int rgqa_odin_dlogits(const float* logits, int ld, const int64_t* label, const float* max_score, int B, int NA, int NAp, float* dlogits, int ldd, float* loss,
+                      void* stream) {
+    return k_odin_dlogits(logits, ld, label, max_score, B, NA, NAp, dlogits, ldd, loss, S(stream));
+}
+int rgqa_sign_step(const float* x, const float* grad, float noise, float* out, size_t n, void* stream) { return k_sign_step(x, grad, noise, out, n, S(stream)); }
 int rgqa_op_bce(const float* logits, const float* target, float* loss, float* dlogits, int B, int NA, void* stream) {
     return k_bce_fwd_bwd(logits, NA, target, NA, loss, dlogits, NA, B, NA, NA, 1.0f, S(stream));
 }

@@ -1013,7 +1013,6 @@ public:
         const int H = cfg.hidden, ni = B * Oi;
         const float pd = cfg.hidden_dropout;
         const DropCfg nodrop = make_drop(0.f, 0, 0);
-        RGQA_REQUIRE(dfeats_out == nullptr && dboxes_out == nullptr, "backward: input gradients are not available for the UNITER backbone");
         // text rows -> text order, LayerNorm backward, scatter into the tables (only the word table has padding_idx, :563-568)
         CKP(PC_OTHER, k_gather_rows<TB>(dy, H, text_dst_dev, 0, u_gt, H, n_text, H, s));
         CKP(PC_LN, k_ln_bwd<TB>(u_gt, H, sv(emb_z), H, P + mp.emb_ln.w, emb_mean, emb_rstd, u_de, nullptr, H, part, G + mp.emb_ln.w, G + mp.emb_ln.b, nullptr, accumulate, n_text, H,
@@ -1027,11 +1026,23 @@ public:
         CKP(PC_LN, k_ln_bwd<TB>(u_dx3, H, sv(u_zp), H, P + mp.box_ln.w, u_st + 2 * ni, u_st + 3 * ni, u_dz, nullptr, H, part, G + mp.box_ln.w, G + mp.box_ln.b, G + mp.box_fc.b, accumulate, ni, H,
                                nodrop, nodrop, 1.0f, s));
         CKP(PC_OTHER, k_pos_wgrad<TB>(u_dz, H, in_boxes, cfg.pos_dim, part, G + mp.box_fc.w, accumulate, ni, H, s));
+        // input gradient dL/dpos [B*O, pos_dim] = u_dz . W_pos while u_dz still holds the gradient entering pos_linear (ODIN, tasks/gqa_odin.py:97-121)
+        if (dboxes_out) CKP(PC_OTHER, k_pos_dgrad<TB>(u_dz, H, P + mp.box_fc.w, cfg.pos_dim, dboxes_out, ni, H, s));
         CKP(PC_LN, k_ln_bwd<TB>(u_dx3, H, sv(u_zf), H, P + mp.visn_ln.w, u_st, u_st + ni, u_dz, nullptr, H, part, G + mp.visn_ln.w, G + mp.visn_ln.b, G + mp.visn_fc.b, accumulate, ni, H,
                                nodrop, nodrop, 1.0f, s));
         GemmGroup g; gg_init(g);
         add_wgrad(g, u_dz, H, mp.visn_fc, 0, H, LP ? (const void*)sv(feats_lp) : (const void*)in_feats, cfg.feat_dim, ni, accumulate);
-        return run_wgrad(g, s);
+        CK(run_wgrad(g, s));
+        if (dfeats_out) {       // input gradient dL/dfeats [B*O, feat_dim] f32 = u_dz . W_img_linear: the f32-output dgrad GEMM of the LXMERT path
+            gg_init(g);
+            add_dgrad(g, u_dz, H, mp.visn_fc, 0, H, dfeats_out, cfg.feat_dim, ni, EPI_BIAS, nullptr, 0);
+            double f, b; gemm_work_t<TB>(g, f, b);
+            prof_begin(PC_GEMM_NT_D, f, b, s);
+            int r = nt_gemm_b(g, 1, 1, s);
+            prof_end(s);
+            CK(r);
+        }
+        return RGQA_OK;
     }
 
     int forward(const float* feats, const float* boxes, const int64_t* ids, const int64_t* seg, const int64_t* mask,

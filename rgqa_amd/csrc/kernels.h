@@ -104,6 +104,7 @@ int k_make_mask(const int64_t* input_mask, float* out, int n, hipStream_t s);
 int k_uniter_dst(const int* tcu, const int* jcu, int B, int O, int* text_dst, int* img_dst, hipStream_t s);
 int k_uniter_mask(const int64_t* input_mask, float* out, int B, int T, int O, hipStream_t s);
 template <typename T> int k_pos_proj(const float* pos, int pd, const float* Wp, const float* bp, T* out, int ldo, int M, int H, hipStream_t s);
+template <typename T> int k_pos_dgrad(const T* dzp, int ld, const float* Wp, int pd, float* dpos, int M, int H, hipStream_t s);
 template <typename T> int k_pos_wgrad(const T* dzp, int ld, const float* pos, int pd, float* part, float* dWp, int accumulate, int M, int H, hipStream_t s);
 template <typename T>
 int k_sum3_ln_fwd(const T* a, const T* b, int ld, const float* trow, const float* gamma, const float* beta, const int* dst, T* out, int ldo, T* xsave, float* mean, float* rstd,
@@ -163,6 +164,9 @@ int k_batch_prepare(const void* feats_in, int feats_f16, float* feats_out, const
 // test-time scoring of logits rows (score.hip)
 int k_score_rows(const float* logits, int ld, int B, int NA, float temperature, int k, float* max_score, int64_t* label, float* energy,
                  float* topk_val, int64_t* topk_idx, float* topk_energy, hipStream_t s);
+// the two steps ODIN adds to the scorer (tasks/gqa_odin.py:101-121; score.hip)
+int k_odin_dlogits(const float* logits, int ld, const int64_t* label, const float* max_score, int B, int NA, int NAp, float* dlogits, int ldd, float* loss, hipStream_t s);
+int k_sign_step(const float* x, const float* grad, float noise, float* out, size_t n, hipStream_t s);
 int k_mixup_gather(float* feats, float* boxes, const int32_t* partner, const uint8_t* take_pos /*[B,O]*/, int B, int O, int F, int mode_v3, hipStream_t s);
 int k_mixup_perturb(float* feats, float* boxes, const int32_t* perm, int B, int O, int F, hipStream_t s);
 int k_mixup_weighted_sum(float* feats, float* boxes, const int32_t* partner, const float* p, const float* q, int B, int O, int F, hipStream_t s);

@@ -85,6 +85,35 @@ int k_pos_wgrad(const T* dzp, int ld, const float* pos, int pd, float* part, flo
     return k_colsum_finalize(part, nblk, pd, H, fo, accumulate, s);
 }
 
+// dpos[row, k] = sum_n dzp[row, n] Wp[n, k]: the input gradient of pos_linear (ODIN, tasks/gqa_odin.py:97-121), one wave per row
+template <typename T>
+__global__ __launch_bounds__(256) void pos_dgrad_kernel(const T* __restrict__ dzp, int ld, const float* __restrict__ Wp, int pd, float* __restrict__ dpos, int M, int H) {
+    const int lane = threadIdx.x & 63;
+    const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= M) return;                               // wave-uniform
+    float acc[UNITER_MAXPOS];
+#pragma unroll
+    for (int k = 0; k < UNITER_MAXPOS; ++k) acc[k] = 0.f;
+    for (int n = lane; n < H; n += 64) {
+        const float g = ld_elem(dzp + (size_t)row * ld + n);
+#pragma unroll
+        for (int k = 0; k < UNITER_MAXPOS; ++k) if (k < pd) acc[k] = fmaf(g, Wp[(size_t)n * pd + k], acc[k]);
+    }
+#pragma unroll
+    for (int k = 0; k < UNITER_MAXPOS; ++k) {
+        const float t = wave_sum(acc[k]);
+        if (lane == k && k < pd) dpos[(size_t)row * pd + k] = t;
+    }
+}
+template <typename T>
+int k_pos_dgrad(const T* dzp, int ld, const float* Wp, int pd, float* dpos, int M, int H, hipStream_t s) {
+    RGQA_REQUIRE(pd >= 1 && pd <= UNITER_MAXPOS, "pos_dgrad: pos_dim %d unsupported", pd);
+    if (M <= 0) return RGQA_OK;
+    hipLaunchKernelGGL(pos_dgrad_kernel<T>, dim3(cdiv(M, 4)), dim3(256), 0, s, dzp, ld, Wp, pd, dpos, M, H);
+    RGQA_LAUNCH_CHECK("pos_dgrad_kernel");
+    return RGQA_OK;
+}
+
 // x3[row] = a[row] + b[row] + trow;  out[dst[row]] = dropout(LN(x3[row]));  x3 and the statistics are kept per LOCAL row (the
 // LayerNorm backward runs on the contiguous image rows); the dropout stream is indexed by the local row as well
 template <typename T, int NV>
@@ -158,6 +187,9 @@ template int k_pos_proj<sf32>(const float*, int, const float*, const float*, sf3
 template int k_pos_wgrad<float>(const float*, int, const float*, int, float*, float*, int, int, int, hipStream_t);
 template int k_pos_wgrad<bf16_t>(const bf16_t*, int, const float*, int, float*, float*, int, int, int, hipStream_t);
 template int k_pos_wgrad<sf32>(const sf32*, int, const float*, int, float*, float*, int, int, int, hipStream_t);
+template int k_pos_dgrad<float>(const float*, int, const float*, int, float*, int, int, hipStream_t);
+template int k_pos_dgrad<bf16_t>(const bf16_t*, int, const float*, int, float*, int, int, hipStream_t);
+template int k_pos_dgrad<sf32>(const sf32*, int, const float*, int, float*, int, int, hipStream_t);
 template int k_sum3_ln_fwd<float>(const float*, const float*, int, const float*, const float*, const float*, const int*, float*, int, float*, float*, float*, int, int, float, DropCfg, hipStream_t);
 template int k_sum3_ln_fwd<bf16_t>(const bf16_t*, const bf16_t*, int, const float*, const float*, const float*, const int*, bf16_t*, int, bf16_t*, float*, float*, int, int, float, DropCfg, hipStream_t);
 template int k_sum3_ln_fwd<sf32>(const sf32*, const sf32*, int, const float*, const float*, const float*, const int*, sf32*, int, sf32*, float*, float*, int, int, float, DropCfg, hipStream_t);

@@ -283,7 +283,8 @@ class Engine:
 
     def set_input_grads(self, dfeats=None, dboxes=None):
         """f32 device tensors [B*O, feat_dim] / [B*O, pos_dim] (or None) that the following backward calls fill with dL/dfeats and
-        dL/dboxes (the reference's ODIN scorer, tasks/gqa_odin.py:97-121)."""
+        dL/dboxes (the reference's ODIN scorer, tasks/gqa_odin.py:97-121).  Every backbone (UNITER: dboxes is dL/dpos, pos_dim = 7); parameter
+        gradients are bit-identical with and without the buffers."""
         for t in (dfeats, dboxes):
             if t is not None and (t.dtype != torch.float32 or not t.is_contiguous() or t.device != self.device):
                 raise ValueError("input-gradient buffers must be contiguous f32 tensors on %s" % self.device)

@@ -10,6 +10,7 @@ The module tree below only CARRIES parameters (real nn.Linear / nn.Embedding / n
 backward runs in librgqa_hip.so on flat arenas that these parameters are views of.  No CPU path: calling forward
 without an MI355X / the built library raises.
 """
+import contextlib
 import copy
 import json
 import logging
@@ -341,6 +342,21 @@ def _dp_exchanging(world=None):
     return w > 1 or os.environ.get("RGQA_DP_REHEARSAL") == "1"
 
 
+_SCORING_DEPTH = 0      # a plain module global: autograd runs backward() on a thread of its own, inside the caller's `with` block
+
+
+@contextlib.contextmanager
+def scoring_pass():
+    """Backward passes inside this block belong to a test-time scorer (rgqa_amd.scoring.odin_scores): they never run the data-parallel
+    exchange, whatever `module.training` says (the reference scores BUTD in train() mode, tasks/gqa_odin.py:87-88)."""
+    global _SCORING_DEPTH
+    _SCORING_DEPTH += 1
+    try:
+        yield
+    finally:
+        _SCORING_DEPTH -= 1
+
+
 class _EngineFunction(torch.autograd.Function):
     """Autograd boundary: forward and backward of the whole encoder (+ optional fused answer head) are single engine
     calls; parameter gradients are written straight into the gradient arena that the parameters' .grad view."""
@@ -389,8 +405,9 @@ class _EngineFunction(torch.autograd.Function):
         rank, world = _dp_rank_world()
         # The exchange belongs to TRAINING steps only: a backward in eval() mode (the test-time scorers that differentiate w.r.t. the
         # inputs, tasks/gqa_odin.py:97-121, run under model.eval()) exchanges nothing - ranks may then run different numbers of passes
-        # without deadlocking, and no 819-MB collective rides on a scoring pass.
-        dp = _dp_exchanging(world) and owner.training
+        # without deadlocking, and no 819-MB collective rides on a scoring pass.  The reference scores BUTD in train() mode: scoring.odin_scores
+        # marks its pass (scoring_pass), which exchanges nothing either.
+        dp = _dp_exchanging(world) and owner.training and _SCORING_DEPTH == 0
         if not dp:
             world = 1
         if dp:
