@@ -76,7 +76,9 @@ int rgqa_version(void);
  * key 21: bf16x3_fwd precision, 1 (default) = the LayerNorm backward reads the hi parts of the split-f32 pre-LayerNorm sums in place, 0 = a bf16 image of them is
  * stored by the projections' epilogues (round 5); bit-identical gradients;
  * key 22: persistent NT GEMM launches: the blocks that walk one tile fewer than the busiest ones start late by value / 16 x K-steps x ~2 us (inside their slack), so that
- * their K loops run beside the other blocks' tile stores; 0 = every block starts at once (rounds 1-5); default 8; same results. */
+ * their K loops run beside the other blocks' tile stores; 0 = every block starts at once (rounds 1-5); default 8; same results;
+ * key 23: MFMA attention kernels on packed rows: 1 (default) = a wave whose sample fills one 16-row tile fewer than the launch's tile counts (per dimension) runs the
+ * body of the smaller count, 0 = every wave runs the launch's full tile counts; bit-identical results. */
 int rgqa_debug_set(int key, int value);
 /* The library runs the deferred weight-gradient GEMMs on ONE side stream per device, shared by every engine of the process.  By default it makes
  * that stream itself when the first engine is bound; a caller that knows better hands one in BEFORE that (the Python binding does: HIP maps streams
@@ -355,6 +357,13 @@ int rgqa_op_attention(const void* qkv, const float* mask /* [B,L] additive or nu
                       int nh, int L, int dh, int dtype, int impl, void* stream);
 int rgqa_op_attention_bwd(const void* qkv, const float* mask, const float* lse, const void* dout, void* dqkv, int B,
                           int nh, int L, int dh, int dtype, int impl, void* stream);
+/* Attention (head size 64) over row windows: q rows [.., nh*64] with row stride ldq elements, k | v rows [.., 2*nh*64] (k at column 0, v at column
+ * nh*64) with row stride ldkv; cu_q / cu_k: device int32[B+1], sample b owns rows cu[b] .. cu[b+1]-1 (at most Lq / Lk of them), or null = rows
+ * b*Lq .. / b*Lk ..  out / dout / dq: [.., nh*64] dense, dkv: [.., 2*nh*64] dense.  dtype / impl as rgqa_op_attention. */
+int rgqa_op_attention_rows(const void* q, int ldq, const void* kv, int ldkv, const int* cu_q, const int* cu_k, const float* mask, void* out, float* lse,
+                           int B, int nh, int Lq, int Lk, int dtype, int impl, void* stream);
+int rgqa_op_attention_rows_bwd(const void* q, int ldq, const void* kv, int ldkv, const int* cu_q, const int* cu_k, const float* mask, const float* lse,
+                               const void* dout, void* dq, void* dkv, int B, int nh, int Lq, int Lk, int dtype, int impl, void* stream);
 int rgqa_op_bce(const float* logits, const float* target, float* loss, float* dlogits, int B, int NA, void* stream);
 
 #ifdef __cplusplus

@@ -21,9 +21,20 @@ typedef __attribute__((address_space(3))) bf16x4 lds_bf16x4;
 // Rows past the sample's length are read from its LAST valid row instead of being zero-filled under a branch (4 v_mov + an exec-mask
 // branch per fragment: 8-9 % of these kernels' instructions): whatever such a row holds is finite and only ever multiplies a probability
 // that is exactly 0 (masked key: exp(-inf); query row past Lq: forced to 0 in the backward kernels, never stored in the forward one).
-__device__ __forceinline__ bf16x8 ldfrag(const bf16_t* base, int row, int nrows, int ld, int s, int g) {
-    const int r = row < nrows ? row : nrows - 1;
-    return *reinterpret_cast<const bf16x8*>(base + (size_t)r * ld + s * 32 + g * 8);
+// `base` = element (row 0, dim 0) of the head (wave-uniform), off = the lane's byte offset attn_row_off(row, nrows, 2 * ld, 16 * g) (kernels.h: the clamp is there)
+__device__ __forceinline__ bf16x8 ldfrag(const unsigned char* base, uint32_t off, int s) {
+    return *reinterpret_cast<const bf16x8*>(base + off + s * 64);
+}
+__device__ __forceinline__ const unsigned char* head_base(const void* p, size_t row0, int ld, int h) {
+    return reinterpret_cast<const unsigned char*>(reinterpret_cast<const bf16_t*>(p) + row0 * ld + h * 64);
+}
+__device__ __forceinline__ unsigned char* head_base(void* p, size_t row0, int ld, int h) {
+    return reinterpret_cast<unsigned char*>(reinterpret_cast<bf16_t*>(p) + row0 * ld + h * 64);
+}
+// 4 consecutive elements dt * 16 + 4 g .. + 3 of a bf16 output row, as they leave an accumulator tile
+__device__ __forceinline__ bf16x4 cvt4_b(const f32x4& o) {
+    bf16x4 t; t[0] = (bf16_t)o[0]; t[1] = (bf16_t)o[1]; t[2] = (bf16_t)o[2]; t[3] = (bf16_t)o[3];
+    return t;
 }
 // transposed fragment: element jj = tile[ (jj<4 ? r0a : r0b) + 4*g + (jj&3) ][ c0 + (lane&15) ]
 template <int PITCH = ROWB>
@@ -57,20 +68,25 @@ __device__ __forceinline__ void attn_fwd_mfma_body(const AttnArgs& a, const int 
     const int lane = threadIdx.x, fr = lane & 15, g = lane >> 4;
     const int b = blk / a.nh, h = blk % a.nh;
     ATTN_SAMPLE_ROWS(a, b)      // q0, k0: first row of this sample; Lq, Lk: its valid row counts (<= a.Lq, a.Lk)
-    const bf16_t* Q = reinterpret_cast<const bf16_t*>(a.q) + q0 * a.ldq + h * 64;
-    const bf16_t* K = reinterpret_cast<const bf16_t*>(a.k) + k0 * a.ldk + h * 64;
-    const bf16_t* V = reinterpret_cast<const bf16_t*>(a.v) + k0 * a.ldv + h * 64;
+    const unsigned char* Q = head_base(a.q, q0, a.ldq, h);
+    const unsigned char* K = head_base(a.k, k0, a.ldk, h);
+    const unsigned char* V = head_base(a.v, k0, a.ldv, h);
+    const uint32_t pk = 2 * (uint32_t)a.ldk, pv = 2 * (uint32_t)a.ldv, pq = 2 * (uint32_t)a.ldq;      // row pitches in bytes
     // one global-load phase: Q, K, V fragments and the mask requested back to back; the V image for the transposed reads is
     // written from the V registers
     bf16x8 qf[NQT][2], kf[NKT][2], vf[NKT][2];
 #pragma unroll
-    for (int kt = 0; kt < NKT; ++kt)
+    for (int kt = 0; kt < NKT; ++kt) {
+        const uint32_t ko = attn_row_off(kt * 16 + fr, Lk, pk, 16 * g), vo = attn_row_off(kt * 16 + fr, Lk, pv, 16 * g);
 #pragma unroll
-        for (int s = 0; s < 2; ++s) { kf[kt][s] = ldfrag(K, kt * 16 + fr, Lk, a.ldk, s, g); vf[kt][s] = ldfrag(V, kt * 16 + fr, Lk, a.ldv, s, g); }
+        for (int s = 0; s < 2; ++s) { kf[kt][s] = ldfrag(K, ko, s); vf[kt][s] = ldfrag(V, vo, s); }
+    }
 #pragma unroll
-    for (int qt = 0; qt < NQT; ++qt)
+    for (int qt = 0; qt < NQT; ++qt) {
+        const uint32_t qo = attn_row_off(qt * 16 + fr, Lq, pq, 16 * g);
 #pragma unroll
-        for (int s = 0; s < 2; ++s) qf[qt][s] = ldfrag(Q, qt * 16 + fr, Lq, a.ldq, s, g);
+        for (int s = 0; s < 2; ++s) qf[qt][s] = ldfrag(Q, qo, s);
+    }
     f32x4 acc[NKT][NQT];
     float mk[NKT][4];
 #pragma unroll
@@ -97,9 +113,13 @@ __device__ __forceinline__ void attn_fwd_mfma_body(const AttnArgs& a, const int 
         }
     }
     DropCfg dc = a.drop; dc.seed_hi ^= a.drop_site;
+    // dropout index ((b nh + h) a.Lq + q) a.Lk + key, mod 2^32 as before: the wave's part once (scalar), the lane's fr a.Lk + 4 g once
+    const uint32_t idx_w = (uint32_t)((b * a.nh + h) * a.Lq) * (uint32_t)a.Lk, idx_l = __umul24(fr, a.Lk) + 4 * g;
+    float* lse_w = a.lse ? a.lse + ((size_t)b * a.nh + h) * a.Lq : nullptr;
 #pragma unroll
     for (int qt = 0; qt < NQT; ++qt) {
         const int q = qt * 16 + fr;
+        const uint32_t idx_q = idx_w + idx_l + (uint32_t)(qt * 16) * (uint32_t)a.Lk;
         float m = -INFINITY;
 #pragma unroll
         for (int kt = 0; kt < NKT; ++kt)
@@ -115,12 +135,12 @@ __device__ __forceinline__ void attn_fwd_mfma_body(const AttnArgs& a, const int 
         sum += __shfl_xor(sum, 16, 64);
         sum += __shfl_xor(sum, 32, 64);
         const float inv = 1.f / sum;
-        if (g == 0 && q < Lq && a.lse) a.lse[((size_t)b * a.nh + h) * a.Lq + q] = m + __logf(sum);
+        if (g == 0 && q < Lq && lse_w) lse_w[q] = m + __logf(sum);
 #pragma unroll
         for (int kt = 0; kt < NKT; ++kt)
         {
             // four consecutive keys of one query row: with an even row length the index is even and one hash serves two elements
-            const uint32_t idx = (uint32_t)(((b * a.nh + h) * a.Lq + q) * a.Lk + kt * 16 + 4 * g);
+            const uint32_t idx = idx_q + kt * 16;
             float v[4] = {acc[kt][qt][0] * inv, acc[kt][qt][1] * inv, acc[kt][qt][2] * inv, acc[kt][qt][3] * inv};
             if ((a.Lk & 1) == 0) drop_apply_vec<4>(dc, idx, v);
             else {
@@ -132,7 +152,9 @@ __device__ __forceinline__ void attn_fwd_mfma_body(const AttnArgs& a, const int 
         }
     }
     // ctx^T[d][q] = sum_key V^T[d][key] P^T[key][q]
-    bf16_t* O = reinterpret_cast<bf16_t*>(a.out) + q0 * a.ldo + h * 64;
+    unsigned char* O = head_base(a.out, q0, a.ldo, h);
+    const uint32_t po = 2 * (uint32_t)a.ldo, g16 = attn_pair_off(g);
+    bf16x4 ev[NQT];      // the even dim tile's pieces, held until the odd one completes the 16-byte stores (kernels.h attn_pair16)
     constexpr int NKS = (NKT + 1) / 2;
     const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
@@ -149,9 +171,11 @@ __device__ __forceinline__ void attn_fwd_mfma_body(const AttnArgs& a, const int 
                 o = MFMA(va[ks], pb, o);
             }
             const int q = qt * 16 + fr;
-            if (q < Lq) {
-                float v[4] = {o[0], o[1], o[2], o[3]};
-                store4(O + (size_t)q * a.ldo + dt * 16 + 4 * g, v);
+            const bf16x4 t = cvt4_b(o);
+            if ((dt & 1) == 0) ev[qt] = t;
+            else {
+                const bf16x8 t16 = attn_pair16(ev[qt], t);
+                if (q < Lq) *reinterpret_cast<bf16x8*>(O + (__umul24(q, po) + (dt >> 1) * 64 + g16)) = t16;
             }
         }
     }
@@ -164,6 +188,8 @@ __device__ __forceinline__ void attn_fwd_mfma_body(const AttnArgs& a, const int 
 // dO^T.  The kernel is instruction-issue bound (SQ_ACTIVE_INST_ANY 0.36 per wave at two waves per SIMD): the key-major pass shrinks
 // from ~2200 to ~800 instructions.  dS takes the K image's place once every dQ is done (held packed in registers until then); the Pd
 // image is the only new LDS (pitch NKT * 32 + 16 bytes).
+// (Later measurement, docs/MEASUREMENTS.md 4.9: the 0.36 was waves waiting, not a full issue pipe - a 14 % shorter stream for most language waves moved
+// nothing, 16-byte instead of 8-byte output stores (kernels.h attn_pair16) took 10-17 % off every launch.)
 template <int NQT, int NKT>
 __host__ __device__ constexpr int attn_bwd1_smem() {
     return (NKT * 16 * ROWB > NQT * 16 * (NKT * 32 + 16) ? NKT * 16 * ROWB : NQT * 16 * (NKT * 32 + 16)) + 2 * NQT * 16 * ROWB + NQT * 16 * (NKT * 32 + 16);
@@ -179,24 +205,29 @@ __device__ __forceinline__ void attn_bwd1_mfma_body(const AttnArgs& a, const int
     const int lane = threadIdx.x, fr = lane & 15, g = lane >> 4;
     const int b = blk / a.nh, h = blk % a.nh;
     ATTN_SAMPLE_ROWS(a, b)
-    const bf16_t* Q = reinterpret_cast<const bf16_t*>(a.q) + q0 * a.ldq + h * 64;
-    const bf16_t* K = reinterpret_cast<const bf16_t*>(a.k) + k0 * a.ldk + h * 64;
-    const bf16_t* V = reinterpret_cast<const bf16_t*>(a.v) + k0 * a.ldv + h * 64;
-    const bf16_t* dO = reinterpret_cast<const bf16_t*>(a.dout) + q0 * a.lddo + h * 64;
+    const unsigned char* Q = head_base(a.q, q0, a.ldq, h);
+    const unsigned char* K = head_base(a.k, k0, a.ldk, h);
+    const unsigned char* V = head_base(a.v, k0, a.ldv, h);
+    const unsigned char* dO = head_base(a.dout, q0, a.lddo, h);
     const float* lse = a.lse + ((size_t)b * a.nh + h) * a.Lq;
+    const uint32_t pk = 2 * (uint32_t)a.ldk, pv = 2 * (uint32_t)a.ldv, pq = 2 * (uint32_t)a.ldq, pdo = 2 * (uint32_t)a.lddo;      // row pitches in bytes
     // ONE global-load phase: every operand fragment (both passes use the same 16-B-per-lane row pieces), the log-sum-exp and
     // the key mask are requested back to back; the three LDS images the transposed reads need are then written from those
     // registers.  (The first version re-read K/Q/dO from global for the images and again per pass: ~6 dependent L2/HBM
     // round trips on a 1-wave block.)
     bf16x8 kf[NKT][2], vf[NKT][2], qf[NQT][2], of[NQT][2];
 #pragma unroll
-    for (int kt = 0; kt < NKT; ++kt)
+    for (int kt = 0; kt < NKT; ++kt) {
+        const uint32_t ko = attn_row_off(kt * 16 + fr, Lk, pk, 16 * g), vo = attn_row_off(kt * 16 + fr, Lk, pv, 16 * g);
 #pragma unroll
-        for (int s = 0; s < 2; ++s) { kf[kt][s] = ldfrag(K, kt * 16 + fr, Lk, a.ldk, s, g); vf[kt][s] = ldfrag(V, kt * 16 + fr, Lk, a.ldv, s, g); }
+        for (int s = 0; s < 2; ++s) { kf[kt][s] = ldfrag(K, ko, s); vf[kt][s] = ldfrag(V, vo, s); }
+    }
 #pragma unroll
-    for (int qt = 0; qt < NQT; ++qt)
+    for (int qt = 0; qt < NQT; ++qt) {
+        const uint32_t qo = attn_row_off(qt * 16 + fr, Lq, pq, 16 * g), oo = attn_row_off(qt * 16 + fr, Lq, pdo, 16 * g);
 #pragma unroll
-        for (int s = 0; s < 2; ++s) { qf[qt][s] = ldfrag(Q, qt * 16 + fr, Lq, a.ldq, s, g); of[qt][s] = ldfrag(dO, qt * 16 + fr, Lq, a.lddo, s, g); }
+        for (int s = 0; s < 2; ++s) { qf[qt][s] = ldfrag(Q, qo, s); of[qt][s] = ldfrag(dO, oo, s); }
+    }
     float lse_t[NQT], mk[NKT][4];
 #pragma unroll
     for (int qt = 0; qt < NQT; ++qt) {
@@ -223,17 +254,19 @@ __device__ __forceinline__ void attn_bwd1_mfma_body(const AttnArgs& a, const int
         }
     __syncthreads();
     DropCfg dc = a.drop; dc.seed_hi ^= a.drop_site;
-    const uint32_t idx0 = (uint32_t)((b * a.nh + h) * a.Lq) * (uint32_t)a.Lk;
+    const uint32_t idx0 = (uint32_t)((b * a.nh + h) * a.Lq) * (uint32_t)a.Lk + __umul24(fr, a.Lk) + 4 * g;      // + the lane's fr a.Lk + 4 g
     const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
     constexpr int NKS = (NKT + 1) / 2, NQS = (NQT + 1) / 2;
 
     // ---------------- pass T: lane = query, registers = keys  ->  dQ; Pd -> pd_, dS held packed
     bf16x4 dsh[NQT][NKT];
     {
-        bf16_t* dQ = reinterpret_cast<bf16_t*>(a.dq) + q0 * a.lddq + h * 64;
+        unsigned char* dQ = head_base(a.dq, q0, a.lddq, h);
+        const uint32_t pdq = 2 * (uint32_t)a.lddq, g16 = attn_pair_off(g);
 #pragma unroll
         for (int qt = 0; qt < NQT; ++qt) {
             const int q = qt * 16 + fr;
+            const uint32_t idx_q = idx0 + (uint32_t)(qt * 16) * (uint32_t)a.Lk;
             const bf16x8 qf0 = qf[qt][0], qf1 = qf[qt][1];
             const bf16x8 of0 = of[qt][0], of1 = of[qt][1];
             const float lq = lse_t[qt];
@@ -247,7 +280,7 @@ __device__ __forceinline__ void attn_bwd1_mfma_body(const AttnArgs& a, const int
                 dp4 = MFMA(vf[kt][0], of0, dp4); dp4 = MFMA(vf[kt][1], of1, dp4);
                 float keep4[4] = {1.f, 1.f, 1.f, 1.f};
                 {
-                    const uint32_t idx = idx0 + (uint32_t)(q * a.Lk + kt * 16 + 4 * g);
+                    const uint32_t idx = idx_q + kt * 16;
                     if ((a.Lk & 1) == 0) drop_apply_vec<4>(dc, idx, keep4);
                     else {
 #pragma unroll
@@ -279,6 +312,7 @@ __device__ __forceinline__ void attn_bwd1_mfma_body(const AttnArgs& a, const int
                 dsh[qt][kt][0] = (bf16_t)pp[kt][0]; dsh[qt][kt][1] = (bf16_t)pp[kt][1]; dsh[qt][kt][2] = (bf16_t)pp[kt][2]; dsh[qt][kt][3] = (bf16_t)pp[kt][3];
             }
             // dQ^T[d][q] = sum_key K^T[d][key] dS^T[key][q]
+            bf16x4 ev;      // the even dim tile's piece (kernels.h attn_pair16)
 #pragma unroll
             for (int dt = 0; dt < 4; ++dt) {
                 f32x4 o = {0.f, 0.f, 0.f, 0.f};
@@ -288,9 +322,11 @@ __device__ __forceinline__ void attn_bwd1_mfma_body(const AttnArgs& a, const int
                     const bf16x8 db = pack8(pp[2 * ks], (2 * ks + 1 < NKT) ? pp[(2 * ks + 1 < NKT) ? 2 * ks + 1 : 0] : zero4);
                     o = MFMA(ka, db, o);
                 }
-                if (q < Lq) {
-                    float v[4] = {o[0], o[1], o[2], o[3]};
-                    store4(dQ + (size_t)q * a.lddq + dt * 16 + 4 * g, v);
+                const bf16x4 t = cvt4_b(o);
+                if ((dt & 1) == 0) ev = t;
+                else {
+                    const bf16x8 t16 = attn_pair16(ev, t);
+                    if (q < Lq) *reinterpret_cast<bf16x8*>(dQ + (__umul24(q, pdq) + (dt >> 1) * 64 + g16)) = t16;
                 }
             }
         }
@@ -303,8 +339,9 @@ __device__ __forceinline__ void attn_bwd1_mfma_body(const AttnArgs& a, const int
     __syncthreads();
     // ---------------- pass N: lane = key  ->  dK, dV from the parked dS / Pd
     {
-        bf16_t* dK = reinterpret_cast<bf16_t*>(a.dk) + k0 * a.lddk + h * 64;
-        bf16_t* dV = reinterpret_cast<bf16_t*>(a.dv) + k0 * a.lddv + h * 64;
+        unsigned char* dK = head_base(a.dk, k0, a.lddk, h);
+        unsigned char* dV = head_base(a.dv, k0, a.lddv, h);
+        const uint32_t pdk = 2 * (uint32_t)a.lddk, pdv = 2 * (uint32_t)a.lddv, g16 = attn_pair_off(g);
 #pragma unroll
         for (int kt = 0; kt < NKT; ++kt) {
             const int key = kt * 16 + fr;
@@ -315,6 +352,7 @@ __device__ __forceinline__ void attn_bwd1_mfma_body(const AttnArgs& a, const int
                 dsb[qs] = trfrag<P2>(ks_, 2 * qs * 16, (2 * qs + 1) * 16, two, kt * 16, lane);     // element jj = dS[q(jj)][key]
                 pdb[qs] = trfrag<P2>(pd_, 2 * qs * 16, (2 * qs + 1) * 16, two, kt * 16, lane);
             }
+            bf16x4 evk, evv;
 #pragma unroll
             for (int dt = 0; dt < 4; ++dt) {
                 f32x4 ok = {0.f, 0.f, 0.f, 0.f}, ov = {0.f, 0.f, 0.f, 0.f};
@@ -326,10 +364,14 @@ __device__ __forceinline__ void attn_bwd1_mfma_body(const AttnArgs& a, const int
                     ok = MFMA(qa, dsb[qs], ok);   // dK^T[d][key] = sum_q Q^T[d][q] dS[q][key]
                     ov = MFMA(oa, pdb[qs], ov);   // dV^T[d][key] = sum_q dO^T[d][q] Pd[q][key]
                 }
-                if (key < Lk) {
-                    float v1[4] = {ok[0], ok[1], ok[2], ok[3]}, v2[4] = {ov[0], ov[1], ov[2], ov[3]};
-                    store4(dK + (size_t)key * a.lddk + dt * 16 + 4 * g, v1);
-                    store4(dV + (size_t)key * a.lddv + dt * 16 + 4 * g, v2);
+                const bf16x4 tk = cvt4_b(ok), tv = cvt4_b(ov);
+                if ((dt & 1) == 0) { evk = tk; evv = tv; }
+                else {
+                    const bf16x8 k16 = attn_pair16(evk, tk), v16 = attn_pair16(evv, tv);
+                    if (key < Lk) {
+                        *reinterpret_cast<bf16x8*>(dK + (__umul24(key, pdk) + (dt >> 1) * 64 + g16)) = k16;
+                        *reinterpret_cast<bf16x8*>(dV + (__umul24(key, pdv) + (dt >> 1) * 64 + g16)) = v16;
+                    }
                 }
             }
         }
@@ -342,58 +384,63 @@ static int mfma_check(const AttnArgs& a, bool bwd) {
     RGQA_REQUIRE(a.B > 0 && a.nh > 0 && a.Lq > 0 && a.Lk > 0 && a.Lq <= 64 && a.Lk <= 64, "mfma attention: Lq/Lk must be in 1..64 (got %d %d)", a.Lq, a.Lk);
     RGQA_REQUIRE(a.q && a.k && a.v && (a.ldq % 8) == 0 && (a.ldk % 8) == 0 && (a.ldv % 8) == 0, "mfma attention: null operand or row stride not a multiple of 8");
     RGQA_REQUIRE(((uintptr_t)a.q % 16) == 0 && ((uintptr_t)a.k % 16) == 0 && ((uintptr_t)a.v % 16) == 0, "mfma attention: operands must be 16-byte aligned");
+    // the kernels address a sample's rows with 32-bit lane offsets from a 64-bit wave base (kernels.h ATTN_MAX_LD)
+    RGQA_REQUIRE(a.ldq > 0 && a.ldk > 0 && a.ldv > 0 && a.ldq < ATTN_MAX_LD && a.ldk < ATTN_MAX_LD && a.ldv < ATTN_MAX_LD, "mfma attention: row stride out of range (1 .. %d)", ATTN_MAX_LD - 1);
     if (bwd) {
         RGQA_REQUIRE(a.dout && a.dq && a.dk && a.dv && a.lse, "mfma attention bwd: null operand");
         RGQA_REQUIRE((a.lddo % 8) == 0 && (a.lddq % 4) == 0 && (a.lddk % 4) == 0 && (a.lddv % 4) == 0, "mfma attention bwd: bad row strides");
+        RGQA_REQUIRE(a.lddo > 0 && a.lddq > 0 && a.lddk > 0 && a.lddv > 0 && a.lddo < ATTN_MAX_LD && a.lddq < ATTN_MAX_LD && a.lddk < ATTN_MAX_LD && a.lddv < ATTN_MAX_LD,
+                     "mfma attention bwd: row stride out of range (1 .. %d)", ATTN_MAX_LD - 1);
     } else {
         RGQA_REQUIRE(a.out && (a.ldo % 4) == 0, "mfma attention: null output / bad stride");
+        RGQA_REQUIRE(a.ldo > 0 && a.ldo < ATTN_MAX_LD, "mfma attention: row stride out of range (1 .. %d)", ATTN_MAX_LD - 1);
     }
     return RGQA_OK;
 }
 
 template <int NQT, int NKT>
-__global__ __launch_bounds__(64) void attn_fwd_mfma_kernel(const AttnArgs a) {
+__global__ __launch_bounds__(64) void attn_fwd_mfma_kernel(const AttnArgs a, const int trim) {
     __shared__ __attribute__((aligned(16))) unsigned char smem[NKT * 16 * ROWB];
-    attn_fwd_mfma_body<NQT, NKT>(a, blockIdx.x, smem);
+    ATTN_RUN_TRIMMED(attn_fwd_mfma_body, NQT, NKT, a, blockIdx.x, smem, trim);      // per-sample tile counts: kernels.h
 }
 template <int NQT, int NKT>
-__global__ __launch_bounds__(64) void attn_bwd1_mfma_kernel(const AttnArgs a) {
+__global__ __launch_bounds__(64) void attn_bwd1_mfma_kernel(const AttnArgs a, const int trim) {
     __shared__ __attribute__((aligned(16))) unsigned char smem[attn_bwd1_smem<NQT, NKT>()];
-    attn_bwd1_mfma_body<NQT, NKT>(a, blockIdx.x, smem);
+    ATTN_RUN_TRIMMED(attn_bwd1_mfma_body, NQT, NKT, a, blockIdx.x, smem, trim);
 }
 // two problems in one launch: blocks [0, n0) work on a0 with <Q0, K0> tiles, the rest on a1 with <Q1, K1> (block-uniform branch)
 template <int Q0, int K0, int Q1, int K1>
-__global__ __launch_bounds__(64) void attn_fwd_mfma_pair_kernel(const AttnArgs a0, const AttnArgs a1, const int n0) {
+__global__ __launch_bounds__(64) void attn_fwd_mfma_pair_kernel(const AttnArgs a0, const AttnArgs a1, const int n0, const int trim) {
     __shared__ __attribute__((aligned(16))) unsigned char smem[(K0 > K1 ? K0 : K1) * 16 * ROWB];
-    if ((int)blockIdx.x < n0) attn_fwd_mfma_body<Q0, K0>(a0, blockIdx.x, smem);
-    else attn_fwd_mfma_body<Q1, K1>(a1, blockIdx.x - n0, smem);
+    if ((int)blockIdx.x < n0) ATTN_RUN_TRIMMED(attn_fwd_mfma_body, Q0, K0, a0, blockIdx.x, smem, trim);
+    else ATTN_RUN_TRIMMED(attn_fwd_mfma_body, Q1, K1, a1, blockIdx.x - n0, smem, trim);
 }
 template <int Q0, int K0, int Q1, int K1>
-__global__ __launch_bounds__(64) void attn_bwd1_mfma_pair_kernel(const AttnArgs a0, const AttnArgs a1, const int n0) {
+__global__ __launch_bounds__(64) void attn_bwd1_mfma_pair_kernel(const AttnArgs a0, const AttnArgs a1, const int n0, const int trim) {
     constexpr int S0 = attn_bwd1_smem<Q0, K0>(), S1 = attn_bwd1_smem<Q1, K1>();
     __shared__ __attribute__((aligned(16))) unsigned char smem[S0 > S1 ? S0 : S1];
-    if ((int)blockIdx.x < n0) attn_bwd1_mfma_body<Q0, K0>(a0, blockIdx.x, smem);
-    else attn_bwd1_mfma_body<Q1, K1>(a1, blockIdx.x - n0, smem);
+    if ((int)blockIdx.x < n0) ATTN_RUN_TRIMMED(attn_bwd1_mfma_body, Q0, K0, a0, blockIdx.x, smem, trim);
+    else ATTN_RUN_TRIMMED(attn_bwd1_mfma_body, Q1, K1, a1, blockIdx.x - n0, smem, trim);
 }
 
 #define DISPATCH_TILES(KERNEL, nqt, nkt)                                                                          \
     switch ((nqt) * 8 + (nkt)) {                                                                                  \
-        case 1 * 8 + 1: hipLaunchKernelGGL((KERNEL<1, 1>), grid, dim3(64), 0, s, a); break;                        \
-        case 1 * 8 + 2: hipLaunchKernelGGL((KERNEL<1, 2>), grid, dim3(64), 0, s, a); break;                        \
-        case 1 * 8 + 3: hipLaunchKernelGGL((KERNEL<1, 3>), grid, dim3(64), 0, s, a); break;                        \
-        case 1 * 8 + 4: hipLaunchKernelGGL((KERNEL<1, 4>), grid, dim3(64), 0, s, a); break;                        \
-        case 2 * 8 + 1: hipLaunchKernelGGL((KERNEL<2, 1>), grid, dim3(64), 0, s, a); break;                        \
-        case 2 * 8 + 2: hipLaunchKernelGGL((KERNEL<2, 2>), grid, dim3(64), 0, s, a); break;                        \
-        case 2 * 8 + 3: hipLaunchKernelGGL((KERNEL<2, 3>), grid, dim3(64), 0, s, a); break;                        \
-        case 2 * 8 + 4: hipLaunchKernelGGL((KERNEL<2, 4>), grid, dim3(64), 0, s, a); break;                        \
-        case 3 * 8 + 1: hipLaunchKernelGGL((KERNEL<3, 1>), grid, dim3(64), 0, s, a); break;                        \
-        case 3 * 8 + 2: hipLaunchKernelGGL((KERNEL<3, 2>), grid, dim3(64), 0, s, a); break;                        \
-        case 3 * 8 + 3: hipLaunchKernelGGL((KERNEL<3, 3>), grid, dim3(64), 0, s, a); break;                        \
-        case 3 * 8 + 4: hipLaunchKernelGGL((KERNEL<3, 4>), grid, dim3(64), 0, s, a); break;                        \
-        case 4 * 8 + 1: hipLaunchKernelGGL((KERNEL<4, 1>), grid, dim3(64), 0, s, a); break;                        \
-        case 4 * 8 + 2: hipLaunchKernelGGL((KERNEL<4, 2>), grid, dim3(64), 0, s, a); break;                        \
-        case 4 * 8 + 3: hipLaunchKernelGGL((KERNEL<4, 3>), grid, dim3(64), 0, s, a); break;                        \
-        default: hipLaunchKernelGGL((KERNEL<4, 4>), grid, dim3(64), 0, s, a); break;                               \
+        case 1 * 8 + 1: hipLaunchKernelGGL((KERNEL<1, 1>), grid, dim3(64), 0, s, a, trim); break;                        \
+        case 1 * 8 + 2: hipLaunchKernelGGL((KERNEL<1, 2>), grid, dim3(64), 0, s, a, trim); break;                        \
+        case 1 * 8 + 3: hipLaunchKernelGGL((KERNEL<1, 3>), grid, dim3(64), 0, s, a, trim); break;                        \
+        case 1 * 8 + 4: hipLaunchKernelGGL((KERNEL<1, 4>), grid, dim3(64), 0, s, a, trim); break;                        \
+        case 2 * 8 + 1: hipLaunchKernelGGL((KERNEL<2, 1>), grid, dim3(64), 0, s, a, trim); break;                        \
+        case 2 * 8 + 2: hipLaunchKernelGGL((KERNEL<2, 2>), grid, dim3(64), 0, s, a, trim); break;                        \
+        case 2 * 8 + 3: hipLaunchKernelGGL((KERNEL<2, 3>), grid, dim3(64), 0, s, a, trim); break;                        \
+        case 2 * 8 + 4: hipLaunchKernelGGL((KERNEL<2, 4>), grid, dim3(64), 0, s, a, trim); break;                        \
+        case 3 * 8 + 1: hipLaunchKernelGGL((KERNEL<3, 1>), grid, dim3(64), 0, s, a, trim); break;                        \
+        case 3 * 8 + 2: hipLaunchKernelGGL((KERNEL<3, 2>), grid, dim3(64), 0, s, a, trim); break;                        \
+        case 3 * 8 + 3: hipLaunchKernelGGL((KERNEL<3, 3>), grid, dim3(64), 0, s, a, trim); break;                        \
+        case 3 * 8 + 4: hipLaunchKernelGGL((KERNEL<3, 4>), grid, dim3(64), 0, s, a, trim); break;                        \
+        case 4 * 8 + 1: hipLaunchKernelGGL((KERNEL<4, 1>), grid, dim3(64), 0, s, a, trim); break;                        \
+        case 4 * 8 + 2: hipLaunchKernelGGL((KERNEL<4, 2>), grid, dim3(64), 0, s, a, trim); break;                        \
+        case 4 * 8 + 3: hipLaunchKernelGGL((KERNEL<4, 3>), grid, dim3(64), 0, s, a, trim); break;                        \
+        default: hipLaunchKernelGGL((KERNEL<4, 4>), grid, dim3(64), 0, s, a, trim); break;                               \
     }
 
 int k_attn_fwd_mfma(const AttnArgs& a, hipStream_t s) {
@@ -401,6 +448,7 @@ int k_attn_fwd_mfma(const AttnArgs& a, hipStream_t s) {
     if (r) return r;
     const int nqt = cdiv(a.Lq, 16), nkt = cdiv(a.Lk, 16);
     dim3 grid(a.B * a.nh);
+    const int trim = g_rgqa_attn_trim != 0 && (a.cu_q || a.cu_k);
     DISPATCH_TILES(attn_fwd_mfma_kernel, nqt, nkt)
     RGQA_LAUNCH_CHECK("attn_fwd_mfma_kernel");
     return RGQA_OK;
@@ -411,6 +459,7 @@ int k_attn_bwd_mfma(const AttnArgs& a, hipStream_t s) {
     if (r) return r;
     const int nqt = cdiv(a.Lq, 16), nkt = cdiv(a.Lk, 16);
     dim3 grid(a.B * a.nh);
+    const int trim = g_rgqa_attn_trim != 0 && (a.cu_q || a.cu_k);
     DISPATCH_TILES(attn_bwd1_mfma_kernel, nqt, nkt)
     RGQA_LAUNCH_CHECK("attn_bwd_mfma_kernel");
     return RGQA_OK;
@@ -435,8 +484,9 @@ int k_attn_fwd_mfma_pair(const AttnArgs& x, const AttnArgs& y, hipStream_t s) {
     r = mfma_check(a1, false); if (r) return r;
     const int n0 = a0.B * a0.nh;
     dim3 grid(n0 + a1.B * a1.nh);
-    if (shape == 1) hipLaunchKernelGGL((attn_fwd_mfma_pair_kernel<3, 3, 2, 2>), grid, dim3(64), 0, s, a0, a1, n0);
-    else hipLaunchKernelGGL((attn_fwd_mfma_pair_kernel<3, 2, 2, 3>), grid, dim3(64), 0, s, a0, a1, n0);
+    const int trim = g_rgqa_attn_trim != 0 && (a0.cu_q || a0.cu_k || a1.cu_q || a1.cu_k);
+    if (shape == 1) hipLaunchKernelGGL((attn_fwd_mfma_pair_kernel<3, 3, 2, 2>), grid, dim3(64), 0, s, a0, a1, n0, trim);
+    else hipLaunchKernelGGL((attn_fwd_mfma_pair_kernel<3, 2, 2, 3>), grid, dim3(64), 0, s, a0, a1, n0, trim);
     RGQA_LAUNCH_CHECK("attn_fwd_mfma_pair_kernel");
     return 1;
 }
@@ -449,8 +499,9 @@ int k_attn_bwd_mfma_pair(const AttnArgs& x, const AttnArgs& y, hipStream_t s) {
     r = mfma_check(a1, true); if (r) return r;
     const int n0 = a0.B * a0.nh;
     dim3 grid(n0 + a1.B * a1.nh);
-    if (shape == 1) hipLaunchKernelGGL((attn_bwd1_mfma_pair_kernel<3, 3, 2, 2>), grid, dim3(64), 0, s, a0, a1, n0);
-    else hipLaunchKernelGGL((attn_bwd1_mfma_pair_kernel<3, 2, 2, 3>), grid, dim3(64), 0, s, a0, a1, n0);
+    const int trim = g_rgqa_attn_trim != 0 && (a0.cu_q || a0.cu_k || a1.cu_q || a1.cu_k);
+    if (shape == 1) hipLaunchKernelGGL((attn_bwd1_mfma_pair_kernel<3, 3, 2, 2>), grid, dim3(64), 0, s, a0, a1, n0, trim);
+    else hipLaunchKernelGGL((attn_bwd1_mfma_pair_kernel<3, 2, 2, 3>), grid, dim3(64), 0, s, a0, a1, n0, trim);
     RGQA_LAUNCH_CHECK("attn_bwd1_mfma_pair_kernel");
     return 1;
 }

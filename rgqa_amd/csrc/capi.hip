@@ -58,6 +58,7 @@ int rgqa_debug_set(int key, int value) {
     if (key == 20) { g_rgqa_adam_blocks = value; return RGQA_OK; }
     if (key == 21) { g_rgqa_z_in_place = value; return RGQA_OK; }
     if (key == 22) { g_rgqa_nt_stagger = value; return RGQA_OK; }
+    if (key == 23) { g_rgqa_attn_trim = value; return RGQA_OK; }
     rgqa_set_error("debug_set: unknown key %d", key);
     return RGQA_ERR_ARG;
 }
@@ -403,6 +404,32 @@ int rgqa_op_attention_bwd(const void* qkv, const float* mask, const float* lse, 
     const int H = nh * dh;
     a.lse = const_cast<float*>(lse); a.dout = dout; a.lddo = H;
     a.dq = dqkv; a.dk = (char*)dqkv + (size_t)H * esz; a.dv = (char*)dqkv + (size_t)2 * H * esz; a.lddq = a.lddk = a.lddv = 3 * H;
+    if (dtype == 2) return impl == 1 ? k_attn_bwd_x3(a, S(stream)) : k_attn_bwd_ref<sf32>(a, S(stream));
+    if (dtype == 1) return impl == 1 ? k_attn_bwd_mfma(a, S(stream)) : k_attn_bwd_ref<bf16_t>(a, S(stream));
+    return k_attn_bwd_ref<float>(a, S(stream));
+}
+static void fill_attn_rows(AttnArgs& a, const void* q, int ldq, const void* kv, int ldkv, const int* cu_q, const int* cu_k, const float* mask, int B, int nh, int Lq, int Lk, size_t esz) {
+    memset(&a, 0, sizeof a);
+    const int H = nh * 64;
+    a.q = q; a.k = kv; a.v = (const char*)kv + (size_t)H * esz;
+    a.ldq = ldq; a.ldk = a.ldv = ldkv; a.mask = mask; a.B = B; a.nh = nh; a.Lq = Lq; a.Lk = Lk; a.dh = 64; a.cu_q = cu_q; a.cu_k = cu_k;
+    a.scale = 0.125f; a.drop = make_drop(0.f, 0, 0);
+}
+int rgqa_op_attention_rows(const void* q, int ldq, const void* kv, int ldkv, const int* cu_q, const int* cu_k, const float* mask, void* out, float* lse,
+                           int B, int nh, int Lq, int Lk, int dtype, int impl, void* stream) {
+    AttnArgs a; fill_attn_rows(a, q, ldq, kv, ldkv, cu_q, cu_k, mask, B, nh, Lq, Lk, dtype == 1 ? 2 : 4);
+    a.out = out; a.ldo = nh * 64; a.lse = lse;
+    if (dtype == 2) return impl == 1 ? k_attn_fwd_x3(a, S(stream)) : k_attn_fwd_ref<sf32>(a, S(stream));
+    if (dtype == 1) return impl == 1 ? k_attn_fwd_mfma(a, S(stream)) : k_attn_fwd_ref<bf16_t>(a, S(stream));
+    return k_attn_fwd_ref<float>(a, S(stream));
+}
+int rgqa_op_attention_rows_bwd(const void* q, int ldq, const void* kv, int ldkv, const int* cu_q, const int* cu_k, const float* mask, const float* lse,
+                               const void* dout, void* dq, void* dkv, int B, int nh, int Lq, int Lk, int dtype, int impl, void* stream) {
+    const size_t esz = dtype == 1 ? 2 : 4;
+    AttnArgs a; fill_attn_rows(a, q, ldq, kv, ldkv, cu_q, cu_k, mask, B, nh, Lq, Lk, esz);
+    const int H = nh * 64;
+    a.lse = const_cast<float*>(lse); a.dout = dout; a.lddo = H;
+    a.dq = dq; a.lddq = H; a.dk = dkv; a.dv = (char*)dkv + (size_t)H * esz; a.lddk = a.lddv = 2 * H;
     if (dtype == 2) return impl == 1 ? k_attn_bwd_x3(a, S(stream)) : k_attn_bwd_ref<sf32>(a, S(stream));
     if (dtype == 1) return impl == 1 ? k_attn_bwd_mfma(a, S(stream)) : k_attn_bwd_ref<bf16_t>(a, S(stream));
     return k_attn_bwd_ref<float>(a, S(stream));

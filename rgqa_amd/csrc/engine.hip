@@ -176,6 +176,7 @@ int g_rgqa_wgrad_sets = 0;     // rgqa_debug_set(17, v): gradient-buffer sets pl
 int g_rgqa_z_in_place = 1;   // rgqa_debug_set(21, v): bf16x3_fwd precision: 1 (default) = the LayerNorm backward reads the pre-LayerNorm sums' hi parts out of the split-f32 tensor, 0 = out of a bf16
                                // image the projections' epilogues store beside it (round 5); the same bits either way; read at the next forward pass
 int g_rgqa_attn_pair = 1;      // rgqa_debug_set(16, v): 0 = the two attention problems of a stage as two launches (the bit-identity test's other arm)
+int g_rgqa_attn_trim = 1;      // rgqa_debug_set(23, v): 0 = every attention wave runs its launch's full tile counts, 1 = per-sample tile counts with packed rows (kernels.h; bit-identical)
 
 // RGQA_ATTN_REF (test switch: the plain attention kernels instead of the MFMA ones), read once
 static bool attn_ref_forced() { static const bool v = getenv("RGQA_ATTN_REF") != nullptr; return v; }

@@ -67,6 +67,62 @@ struct AttnArgs {
     int Lq = (a).Lq, Lk = (a).Lk;                                                                \
     if ((a).cu_q) { const int c0_ = (a).cu_q[(b)]; q0 = (size_t)c0_; Lq = (a).cu_q[(b) + 1] - c0_; } \
     if ((a).cu_k) { const int c0_ = (a).cu_k[(b)]; k0 = (size_t)c0_; Lk = (a).cu_k[(b) + 1] - c0_; }
+// ---- shared by the MFMA cores (attn_mfma.hip, attn_x3.hip): one wave per (sample, head), instruction-issue bound
+// Per-sample tile counts (rgqa_debug_set key 23; 1 = default): with packed rows a wave knows its own sample's Lq / Lk, and a sample that fills one
+// 16-row tile fewer than the launch's <NQT, NKT> in a dimension runs the body instantiated for that count.  Every dimension is trimmed by at most ONE
+// tile (<= 4 bodies per problem: the 20- and 30-token questions of GQA run <1,*> / <*,1> bodies when they have <= 16 tokens, UNITER's 56-row sequences
+// <3,*> / <*,3> when they have <= 48 rows); the dropped tile only ever held masked keys (probabilities exactly 0, entering the P V / dS K products as
+// the zero half those already have for an odd tile count) and query rows that are never stored, and the dropout index keeps the launch-level a.Lq / a.Lk:
+// results are bit-identical.  Static LDS and registers stay at the launch's maximum.  -DATTN_NO_TRIM (tools/attn_isa_counts.py --notrim) compiles every
+// kernel with the one body of its own tile counts.
+extern int g_rgqa_attn_trim;
+#ifdef ATTN_NO_TRIM
+#define ATTN_RUN_TRIMMED(BODY, NQT, NKT, a, blk, smem, trim) BODY<(NQT), (NKT)>(a, blk, smem)
+#else
+#define ATTN_RUN_TRIMMED(BODY, NQT, NKT, a, blk, smem, trim)                                                             \
+    do {                                                                                                                 \
+        constexpr int QS_ = (NQT) > 1 ? (NQT) - 1 : (NQT), KS_ = (NKT) > 1 ? (NKT) - 1 : (NKT);                          \
+        bool sq_ = false, sk_ = false;                                                                                   \
+        if (trim) {                                                                                                      \
+            const int b_ = (blk) / (a).nh;                                                                               \
+            ATTN_SAMPLE_ROWS(a, b_)                                                                                      \
+            (void)q0; (void)k0;                                                                                          \
+            sq_ = QS_ < (NQT) && Lq <= QS_ * 16; sk_ = KS_ < (NKT) && Lk <= KS_ * 16;                                    \
+        }                                                                                                                \
+        if (sq_ && sk_) BODY<QS_, KS_>(a, blk, smem);                                                                    \
+        else if (sq_) BODY<QS_, (NKT)>(a, blk, smem);                                                                    \
+        else if (sk_) BODY<(NQT), KS_>(a, blk, smem);                                                                    \
+        else BODY<(NQT), (NKT)>(a, blk, smem);                                                                           \
+    } while (0)
+#endif
+// Row addressing without per-fragment 64-bit products (v_mul_lo_u32 / v_mad_u64_u32 issue at quarter rate): the sample's first row and the head go into
+// a wave-uniform 64-bit base (scalar arithmetic), a lane adds the 32-bit byte offset row * (row pitch in bytes) + (its bytes inside the row) of at most
+// 63 rows: ONE full-rate 24-bit multiply-add.  Rows past the sample's length are read from its last valid row (see ldfrag).  The launchers reject row
+// strides of ATTN_MAX_LD elements or more: below it the pitch in bytes (<= 4 per element) fits the 24-bit multiply and 64 rows of it fit 32 bits,
+// whatever the tensor's total extent is.
+#define ATTN_MAX_LD (1 << 22)
+#if defined(__HIPCC__)
+// Output stores of 16 bytes per lane.  An accumulator tile leaves lane (row = lane & 15, g = lane >> 4) with 4 consecutive bf16 values (8 bytes) of dims
+// dt * 16 + 4 g .. + 3; for the two tiles dt = 2 s, 2 s + 1 of a 32-dim step that is bytes 8 g and 32 + 8 g of the step's 64 bytes.  Lanes g and g ^ 1 (16 lanes
+// apart) swap one piece each (v_permlane16_swap: the odd 16-lane rows of `a` <-> the even rows of `b`), after which an even g holds bytes 8 g .. 8 g + 15 and an odd
+// g bytes 32 + 8 (g - 1) .. + 15 (attn_pair_off): half as many store instructions, each 16 bytes per lane.  Every lane of the wave must call it.
+__device__ __forceinline__ bf16x8 attn_pair16(const bf16x4& even_dt, const bf16x4& odd_dt) {
+    union { bf16x4 v; uint32_t u[2]; } a, b;
+    a.v = even_dt; b.v = odd_dt;
+    union { bf16x8 v; uint32_t u[4]; } r;
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+        const auto t = __builtin_amdgcn_permlane16_swap(a.u[i], b.u[i], false, false);
+        r.u[i] = t[0]; r.u[2 + i] = t[1];
+    }
+    return r.v;
+}
+__device__ __forceinline__ uint32_t attn_pair_off(int g) { return 16 * (g >> 1) + 32 * (g & 1); }
+__device__ __forceinline__ uint32_t attn_row_off(int row, int nrows, uint32_t pitch_bytes, uint32_t lane_bytes) {
+    const int r = row < nrows ? row : nrows - 1;
+    return __umul24((uint32_t)r, pitch_bytes) + lane_bytes;
+}
+#endif
 template <typename T> int k_attn_fwd_ref(const AttnArgs& a, hipStream_t s);
 template <typename T> int k_attn_bwd_ref(const AttnArgs& a, hipStream_t s);
 template <typename T> int k_attn_probs(const AttnArgs& a, float* out /* [B, nh, Lq, Lk] */, hipStream_t s);
