@@ -317,6 +317,35 @@ int rgqa_odin_dlogits(const float* logits, int ld, const int64_t* label, const f
  * out may alias x. */
 int rgqa_sign_step(const float* x, const float* grad, float noise, float* out, size_t n, void* stream);
 
+/* ---- the Mahalanobis test method (tasks/gqa_maha.py; rgqa_amd/csrc/maha.hip) ----------------------------------------
+ * The reference scores score[b, c] = -0.5 (x_b - mu_c)^T P (x_b - mu_c) in a loop over the classes (:228-236, :260-268).  Here P is factored once
+ * on the host, P = W W^T (W [H, R] row-major, R = the rank kept), nu = mu W [NC, R], and per batch
+ *     y = pooled W [B, R],   score[b, c] = -0.5 sum_r (y[b, r] - nu[c, r])^2   (differences first, then squares).
+ * All of it is f32 FMA arithmetic on the vector ALU in a fixed summation order, whatever the engine's precision: results repeat bit for bit and a
+ * row's numbers do not depend on B.  scratch: rgqa_maha_scratch_bytes(B, NC) bytes of device memory, any content.
+ *   rgqa_maha_score_rows: pooled [B, H] (row stride ld) -> y [B, R] (dense), score[B], label[B] = gaussian_score.max(1) (:239, :270; ties go to the
+ *     lowest class index, torch.max's first-maximum rule - classes without a sample share the zero mean and tie exactly), and, when all_scores is
+ *     not NULL, the whole matrix [B, NC] with row stride ld_all (nothing is written past column NC).  score / label may be NULL.  A row with a
+ *     non-finite pooled value (or a product pooled W that overflows f32) scores NaN in every class, label 0; a squared distance that overflows f32
+ *     scores -inf for that class alone.
+ *   rgqa_maha_dpooled: d [B, R] (dense) = (pooled_b - mean[label_b]) W and dpooled [B, H] (row stride ldd) = scale * W d_b: with scale = 1 / B the gradient
+ *     w.r.t. the pooled vector of loss = mean_b(-score[b, label_b]) (:240-244), for rgqa_engine_backward_pooled.  mean [NC, H] dense.  The difference is
+ *     taken in the pooled space, as the reference takes it: y_b - nu[label_b] is the same vector, but cancels after the f32 products.  A label outside
+ *     [0, NC) gives a row of zeros.
+ * The estimator (:130-179) accumulates on the device and is finished on the host in f64 (rgqa_amd/scoring.py MahaEstimator.finalize):
+ *   rgqa_maha_accumulate: state = rgqa_maha_state_doubles(NC, H) doubles, zeroed by the caller before the first batch: n[NC] | sums[NC, H] | G[H, H].
+ *     Sample b joins class c whenever target[b, c] != 0 (:158-168): n[c] += 1, sums[c] += pooled[b]; G += k_b pooled[b] pooled[b]^T with k_b the number
+ *     of classes b joined.  f64 accumulators, each owned by one thread that walks b in ascending order: two batches in sequence give the bits of the
+ *     concatenated batch.  H <= 2048. */
+int rgqa_maha_scratch_bytes(int B, int NC, size_t* out);
+int rgqa_maha_score_rows(const float* pooled, int ld, const float* W, const float* nu, int B, int H, int R, int NC, float* y, float* score, int64_t* label,
+                         float* all_scores, int ld_all, void* scratch, size_t scratch_bytes, void* stream);
+int rgqa_maha_dpooled(const float* pooled, int ld, const float* mean, const int64_t* label, const float* W, float scale, int B, int H, int R, int NC, float* d,
+                      float* dpooled, int ldd, void* stream);
+int rgqa_maha_state_doubles(int NC, int H, size_t* out);
+int rgqa_maha_accumulate(const float* pooled, int ld, const float* target, int ld_target, int B, int H, int NC, double* state, void* scratch, size_t scratch_bytes,
+                         void* stream);
+
 /* ---- stand-alone operators (unit parity tests; the engine calls the same kernels internally) ------------- */
 /* dtype of the stand-alone operators: 0 f32, 1 bf16, 2 split f32 (every activation / weight operand in the split layout, ld % 32 == 0).
  * C[M,N] = A[M,K] W[N,K]^T + bias, epilogue 0 none / 1 gelu / 2 tanh (A, W, C all dtype) */

@@ -92,6 +92,11 @@ SIGNATURES = {
     "rgqa_score_rows": [_vp, _i, _i, _i, C.c_float, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "rgqa_odin_dlogits": [_vp, _i, _vp, _vp, _i, _i, _i, _vp, _i, _vp, _vp],
     "rgqa_sign_step": [_vp, _vp, C.c_float, _vp, _sz, _vp],
+    "rgqa_maha_scratch_bytes": [_i, _i, C.POINTER(_sz)],
+    "rgqa_maha_score_rows": [_vp, _i, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _vp, _sz, _vp],
+    "rgqa_maha_dpooled": [_vp, _i, _vp, _vp, _vp, C.c_float, _i, _i, _i, _i, _vp, _vp, _i, _vp],
+    "rgqa_maha_state_doubles": [_i, _i, C.POINTER(_sz)],
+    "rgqa_maha_accumulate": [_vp, _i, _vp, _i, _i, _i, _i, _vp, _vp, _sz, _vp],
     "rgqa_last_error_string": [],
 }
 _RESTYPES = {"rgqa_last_error_string": C.c_char_p, "rgqa_engine_destroy": None, "rgqa_tokenizer_destroy": None, "rgqa_peer_comm_destroy": None}

@@ -13,16 +13,29 @@ backbones:
     featsPt = torch.add(feats.data, (torch.ge(feats.grad, 0).float() - 0.5) * 2, alpha=-noise)             :115-121   sign_step
     the whole batch step: forward, loss gradient, input gradients, perturbed inputs, second forward, score  :97-131    odin_scores
 
+and the Mahalanobis method (tasks/gqa_maha.py) for LXMERT and UNITER, on the pooled vector `GQAModel_maha` / `GQAUNITER_maha` return:
+
+    mean[j] = mean of the pooled rows of the samples with target[i][j] != 0; precision = pinvh(covariance)  :130-183   MahaEstimator, maha_sample_estimator
+    gaussian_score[b, c] = -0.5 (x_b - mean_c)^T precision (x_b - mean_c); .max(1)                          :228-239   maha_score_rows
+    loss = mean(-gaussian_score[b, pred_b]); loss.backward()                                                :240-244   maha_dpooled
+    the whole batch step: forward, score, input step, second forward, score                                 :223-270   maha_scores
+
+with precision = W W^T factored once on the host (csrc/maha.hip).
+
 There is no CPU fallback: without the HIP library this raises."""
 import collections
 import ctypes as C
 
+import numpy as np
 import torch
 
 from . import _lib
 
 Scores = collections.namedtuple("Scores", "max_score label energy topk_values topk_indices topk_energy")
 OdinScores = collections.namedtuple("OdinScores", "score label logits feats_pt boxes_pt")
+MahaPack = collections.namedtuple("MahaPack", "mean precision W nu")
+MahaRows = collections.namedtuple("MahaRows", "score label y all_scores pooled")
+MahaScores = collections.namedtuple("MahaScores", "score label pooled feats_pt boxes_pt")
 
 
 def score_rows(logits, temperature=1.0, k=0):
@@ -124,3 +137,195 @@ def odin_scores(model, feats, boxes, sent, temperature=1.0, noise=0.0):
         logit2 = model(feats_pt, boxes_pt, sent)
     s2 = score_rows(logit2, temperature)
     return OdinScores(s2.max_score, s2.label, logit2, feats_pt, boxes_pt)
+
+
+# ------------------------------------------------------------------------------------------------ Mahalanobis (tasks/gqa_maha.py)
+def maha_factor(precision):
+    """precision [H, H] (symmetrised) -> (W [H, R], P) in numpy f64 with W W^T = P = V diag(lam) V^T over the eigenvalues
+    lam > max(lam) * H * eps(f64): the cut of scipy.linalg.pinvh, which sklearn's EmpiricalCovariance takes its precision_ from.  For a precision
+    matrix that came out of pinvh the cut only drops the null space pinvh left."""
+    P = np.asarray(precision, dtype=np.float64)
+    if P.ndim != 2 or P.shape[0] != P.shape[1]:
+        raise ValueError("maha: precision must be a square matrix")
+    lam, V = np.linalg.eigh((P + P.T) * 0.5)
+    keep = lam > lam.max() * P.shape[0] * np.finfo(np.float64).eps
+    lam, V = lam[keep], V[:, keep]
+    return V * np.sqrt(lam), (V * lam) @ V.T
+
+
+def maha_finalize(n, sums, G):
+    """The host half of the estimator (gqa_maha.py:170-183) in numpy f64, from what `rgqa_maha_accumulate` gathered: n [NC] samples per class,
+    sums [NC, H] their pooled rows added up, G [H, H] = sum over (sample, class) memberships of x x^T.  mean_c = sums_c / n_c (zero for a class
+    without a sample); the rows `X` of the reference are x - mean_c per membership, so X^T X = G - sum_c n_c mean_c mean_c^T and the (biased)
+    covariance is that over sum(n) (sklearn's own re-centring subtracts the mean of X, which is zero in exact arithmetic); precision = pinvh(cov).
+    Returns (mean [NC, H], precision [H, H], W [H, R]) with precision = W W^T."""
+    n, sums, G = np.asarray(n, np.float64), np.asarray(sums, np.float64), np.asarray(G, np.float64)
+    total = n.sum()
+    if total <= 0:
+        raise ValueError("maha: no sample has joined a class")
+    mean = sums / np.maximum(n, 1.0)[:, None]
+    cov = (G - (mean * n[:, None]).T @ mean) / total
+    lam, V = np.linalg.eigh((cov + cov.T) * 0.5)
+    keep = lam > lam.max() * cov.shape[0] * np.finfo(np.float64).eps
+    lam, V = lam[keep], V[:, keep]
+    return mean, (V / lam) @ V.T, V / np.sqrt(lam)
+
+
+def _pack(mean, precision, W, device):
+    mean = np.asarray(mean, np.float64)
+    t = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(device)
+    return MahaPack(t(mean), t(precision), t(W), t(mean @ W))            # nu = mean W in f64, stored as f32
+
+
+def maha_pack(mean, precision, device="cuda"):
+    """The {"mean", "precision"} pair of a reference `sample_estimates.pkl` (tensors or arrays; gqa_maha.py:124-127) -> MahaPack of f32 tensors
+    on `device`: mean [NC, H], precision [H, H], W [H, R] with precision = W W^T, nu = mean W [NC, R]."""
+    mean = mean.detach().cpu().numpy() if isinstance(mean, torch.Tensor) else np.asarray(mean)
+    precision = precision.detach().cpu().numpy() if isinstance(precision, torch.Tensor) else np.asarray(precision)
+    if mean.ndim != 2 or precision.shape != (mean.shape[1], mean.shape[1]):
+        raise ValueError("maha_pack: mean must be [NC, H] and precision [H, H]")
+    W, P = maha_factor(precision)
+    return _pack(mean, P, W, device)
+
+
+def _f32_rows(name, t, cols=None):
+    if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 and t.dim() == 2 and (cols is None or t.shape[1] == cols)):
+        raise ValueError("%s must be a 2-D float32 CUDA tensor%s" % (name, "" if cols is None else " with %d columns" % cols))
+    return t if t.stride(1) == 1 else t.contiguous()
+
+
+def _maha_scratch(B, NC, dev):
+    n = C.c_size_t()
+    _lib.check(_lib.load().rgqa_maha_scratch_bytes(B, NC, C.byref(n)))
+    return torch.empty(n.value, dtype=torch.uint8, device=dev), n.value
+
+
+class MahaEstimator:
+    """gqa_maha.py:130-183: `update(pooled, target)` per training batch (pooled [B, H] f32 CUDA, target [B, NC] f32 CUDA, the UQ column already
+    dropped) accumulates on the device in f64 (`rgqa_maha_accumulate`); `finalize()` reads the state and finishes in numpy f64 -> MahaPack."""
+
+    def __init__(self, num_classes, hidden, device="cuda"):
+        self.num_classes, self.hidden, self.device = int(num_classes), int(hidden), torch.device(device)
+        n = C.c_size_t()
+        _lib.check(_lib.load().rgqa_maha_state_doubles(self.num_classes, self.hidden, C.byref(n)))
+        self.state = torch.zeros(n.value, dtype=torch.float64, device=self.device)
+
+    def update(self, pooled, target):
+        pooled = _f32_rows("MahaEstimator.update: pooled", pooled, self.hidden)
+        target = _f32_rows("MahaEstimator.update: target", target, self.num_classes)
+        if target.shape[0] != pooled.shape[0] or pooled.device != self.state.device or target.device != self.state.device:
+            raise ValueError("MahaEstimator.update: pooled and target must hold the same rows on the estimator's device")
+        B = pooled.shape[0]
+        scratch, nbytes = _maha_scratch(B, self.num_classes, pooled.device)
+        p = _lib.ptr
+        _lib.check(_lib.load().rgqa_maha_accumulate(p(pooled), pooled.stride(0), p(target), target.stride(0), B, self.hidden, self.num_classes, p(self.state),
+                                                    p(scratch), nbytes, _stream(pooled.device)))
+
+    def parts(self):
+        """(n [NC], sums [NC, H], G [H, H]) as numpy f64"""
+        s = self.state.cpu().numpy()
+        NC, H = self.num_classes, self.hidden
+        return s[:NC], s[NC:NC + NC * H].reshape(NC, H), s[NC + NC * H:].reshape(H, H)
+
+    def finalize(self):
+        mean, precision, W = maha_finalize(*self.parts())
+        return _pack(mean, precision, W, self.device)
+
+
+def _maha_model_check(model):
+    from .butd.butd import GQABUTD
+    if isinstance(model, GQABUTD):
+        raise NotImplementedError("maha: the BUTD backbone is not supported: the reference's GQABUTD_maha scores `joint_repr`, and the BUTD engine has no "
+                                  "backward from it (no backward_pooled); use GQAModel_maha or GQAUNITER_maha")
+
+
+def _maha_forward(model, feats, boxes, sent):
+    out = model(feats, boxes, sent)
+    if not (isinstance(out, tuple) and len(out) == 2):
+        raise ValueError("maha: the model must return (logit, pooled) as GQAModel_maha / GQAUNITER_maha do")
+    return out[1]
+
+
+def maha_sample_estimator(model, batches):
+    """gqa_maha.py:130-189 through a drop-in `GQAModel_maha` / `GQAUNITER_maha`: batches yields (feats, boxes, sent, target) with the UQ column of
+    target already dropped (:141).  Runs under eval() and no_grad, restores the model's mode, returns the MahaPack."""
+    _maha_model_check(model)
+    was_training = model.training
+    model.eval()
+    est = None
+    try:
+        with torch.no_grad():
+            for feats, boxes, sent, target in batches:
+                x = _maha_forward(model, feats, boxes, sent)
+                if est is None:
+                    est = MahaEstimator(target.shape[1], x.shape[1], x.device)
+                est.update(x, target.to(x.device, torch.float32))
+    finally:
+        model.train(was_training)
+    if est is None:
+        raise ValueError("maha_sample_estimator: no batches")
+    return est.finalize()
+
+
+def maha_score_rows(pooled, pack, all_scores=False):
+    """pooled: f32 CUDA [B, H] (any row stride).  Returns MahaRows(score [B], label [B] int64, y [B, R], all_scores [B, NC] or None, pooled):
+    score, label = gaussian_score.max(1) of gqa_maha.py:228-239 (ties: the lowest class), y = pooled W, pooled = the input, for `maha_dpooled`."""
+    H, R = pack.W.shape
+    NC = pack.nu.shape[0]
+    pooled = _f32_rows("maha_score_rows: pooled", pooled, H)
+    if pack.W.device != pooled.device:
+        raise ValueError("maha_score_rows: the pack lives on another device")
+    B, dev = pooled.shape[0], pooled.device
+    y = torch.empty(B, R, dtype=torch.float32, device=dev)
+    score = torch.empty(B, dtype=torch.float32, device=dev)
+    label = torch.empty(B, dtype=torch.int64, device=dev)
+    full = torch.empty(B, NC, dtype=torch.float32, device=dev) if all_scores else None
+    scratch, nbytes = _maha_scratch(B, NC, dev)
+    p = _lib.ptr
+    _lib.check(_lib.load().rgqa_maha_score_rows(p(pooled), pooled.stride(0), p(pack.W), p(pack.nu), B, H, R, NC, p(y), p(score), p(label), p(full), NC if all_scores else 0,
+                                                p(scratch), nbytes, _stream(dev)))
+    return MahaRows(score, label, y, full, pooled)
+
+
+def maha_dpooled(rows, pack):
+    """d loss / d pooled [B, H] of loss = mean_b(-gaussian_score[b, label_b]) (gqa_maha.py:239-244) for the MahaRows of `maha_score_rows`:
+    (1 / B) W W^T (pooled_b - mean[label_b]), the difference taken first as the reference takes it."""
+    H, R = pack.W.shape
+    NC = pack.nu.shape[0]
+    x = _f32_rows("maha_dpooled: rows.pooled", rows.pooled, H)
+    B = x.shape[0]
+    if not isinstance(rows.label, torch.Tensor) or rows.label.dtype != torch.int64 or rows.label.shape != (B,) or rows.label.device != x.device or pack.W.device != x.device:
+        raise ValueError("maha_dpooled: rows.label must be an int64 [B] tensor on the device of rows.pooled and the pack")
+    label = rows.label.contiguous()
+    d = torch.empty(B, R, dtype=torch.float32, device=x.device)
+    out = torch.empty(B, H, dtype=torch.float32, device=x.device)
+    p = _lib.ptr
+    _lib.check(_lib.load().rgqa_maha_dpooled(p(x), x.stride(0), p(pack.mean), p(label), p(pack.W), 1.0 / B, B, H, R, NC, p(d), p(out), H,
+                                             _stream(x.device)))
+    return out
+
+
+def maha_scores(model, feats, boxes, sent, pack, noise=0.0):
+    """One batch of the reference's Mahalanobis scorer (gqa_maha.py:223-270) for `GQAModel_maha` or `GQAUNITER_maha` (drop-in classes): forward,
+    `maha_score_rows`, `maha_dpooled`, backward from the pooled output with input gradients, two `sign_step`s, a second forward under no_grad on the
+    perturbed inputs, `maha_score_rows`.  Returns MahaScores(score, label, pooled, feats_pt, boxes_pt): score / label = noised_gaussian_score.max(1)
+    of the SECOND pass, its pooled vectors, and the perturbed inputs.  (`--temperature` is passed by the reference's script and never read.)
+
+    `model.training` is honoured as the caller set it (the reference scores LXMERT / UNITER in eval()); the pass never runs the data-parallel gradient
+    exchange.  Afterwards the parameters' `.grad` hold the scoring pass's gradients, as after the reference's `loss.backward()`.  BUTD raises
+    NotImplementedError."""
+    from .lxrt.modeling import scoring_pass
+    _maha_model_check(model)
+    f = feats.detach().contiguous().float().requires_grad_(True)
+    b = boxes.detach().contiguous().float().requires_grad_(True)
+    with scoring_pass():
+        with torch.enable_grad():
+            x = _maha_forward(model, f, b, sent)
+        rows = maha_score_rows(x.detach(), pack)
+        x.backward(maha_dpooled(rows, pack))
+    feats_pt = sign_step(f.detach(), f.grad, noise)
+    boxes_pt = sign_step(b.detach(), b.grad, noise)
+    with torch.no_grad():
+        x2 = _maha_forward(model, feats_pt, boxes_pt, sent)
+    r2 = maha_score_rows(x2, pack)
+    return MahaScores(r2.score, r2.label, x2, feats_pt, boxes_pt)

@@ -161,3 +161,64 @@ def uniter_batch(cfgd, T, B, O, seed):
     w, h = bx[:, :, 2] - bx[:, :, 0], bx[:, :, 3] - bx[:, :, 1]
     b["pos7"] = np.stack([bx[:, :, 0], bx[:, :, 1], bx[:, :, 2], bx[:, :, 3], w, h, w * h], 2).astype(np.float32)
     return b
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# The Mahalanobis fixture (tests/golden/g13_maha.npz, tools/gen_g13_maha.py): a synthetic training set for the estimator (tasks/gqa_maha.py:130-189)
+# and a test batch for the scorer (:223-270).  Questions are sentences of whole words of tests/golden/g4_vocab.txt, so the drop-in classes
+# (which tokenise strings) and the engine (which takes ids) see the same tokens.
+MAHA_WORDS = ("the is what color of a an on in to left right man woman dog cat table who red blue green are there any or and side which kind "
+              "animal furniture do you see both that this it made wood cafe shirt photo not bottle near behind front top bottom").split()
+MAHA_NC, MAHA_T, MAHA_O, MAHA_TRAIN, MAHA_TEST, MAHA_BATCH, MAHA_NOISE = 23, 8, 6, 512, 8, 64, 1e-4
+MAHA_EMPTY = (5, 22)                                       # classes no training sample joins: they keep the zero mean and tie exactly
+MAHA_CFG = {"lxmert": dict(SMALL, vocab_size=80, max_pos=64), "uniter": dict(U_SMALL, vocab_size=80, max_pos=64)}
+
+
+def maha_fill(shapes):
+    """The fixture's weights: the deterministic filler with every Linear / embedding weight times 6 (the pooler's times 4).  Under the filler's own
+    0.02 initializer range the pooled vector barely moves between samples (std 2e-3 around values of 0.13) and its covariance has a condition number
+    near 5e7; at unit-gain weights the pooled vectors spread (std 0.2) and the within-class covariance is conditioned below 1e4."""
+    out = fill_state_dict(shapes)
+    for k, v in out.items():
+        leaf = k.rsplit(".", 1)[-1]
+        parent = k.rsplit(".", 2)[-2] if k.count(".") >= 1 else ""
+        if "LayerNorm" in parent or "layer_norm" in parent or k.startswith("logit_fc.2.") or leaf == "bias":
+            continue
+        out[k] = (v * np.float32(4.0 if ".pooler." in k else 6.0)).astype(np.float32)
+    return out
+
+
+def maha_sentences(tag, n):
+    nw = 1 + (hash_u32(tag + ".nw", n) % np.uint64(MAHA_T - 2)).astype(np.int64)          # 1 .. T-2 words + [CLS] + [SEP]
+    w = (hash_u32(tag + ".w", n * MAHA_T) % np.uint64(len(MAHA_WORDS))).astype(np.int64).reshape(n, MAHA_T)
+    return [" ".join(MAHA_WORDS[j] for j in w[i, :nw[i]]) for i in range(n)]
+
+
+def maha_targets(tag, n):
+    """soft targets [n, MAHA_NC]: one class at score 1.0, for a quarter of the rows a second one at 0.5, one row in twenty in no class"""
+    t = np.zeros((n, MAHA_NC), dtype=np.float32)
+    c1 = (hash_u32(tag + ".c1", n) % np.uint64(MAHA_NC - 2)).astype(np.int64)
+    c2 = (hash_u32(tag + ".c2", n) % np.uint64(MAHA_NC - 2)).astype(np.int64)
+    two = uniform(tag + ".two", (n,), 0.0, 1.0) < 0.25
+    none = uniform(tag + ".none", (n,), 0.0, 1.0) < 0.05
+    live = [c for c in range(MAHA_NC) if c not in MAHA_EMPTY]
+    for i in range(n):
+        if none[i]:
+            continue
+        t[i, live[c1[i]]] = 1.0
+        if two[i] and c2[i] != c1[i]:
+            t[i, live[c2[i]]] = 0.5
+    return t
+
+
+def maha_case(backbone, part):
+    """backbone 'lxmert' | 'uniter', part 'train' | 'test' -> dict(feats, boxes (UNITER: the 7-d position features), sents, target)"""
+    cfgd = MAHA_CFG[backbone]
+    n = MAHA_TRAIN if part == "train" else MAHA_TEST
+    tag = "maha.%s.%s" % (backbone, part)
+    b = synth_batch(n, MAHA_T, O=MAHA_O, F=cfgd["feat_dim"], NA=MAHA_NC, vocab=cfgd["vocab_size"], seed=1300 + zlib.crc32(tag.encode()) % 97)
+    boxes = b["boxes"]
+    if backbone == "uniter":
+        w, h = boxes[:, :, 2] - boxes[:, :, 0], boxes[:, :, 3] - boxes[:, :, 1]
+        boxes = np.stack([boxes[:, :, 0], boxes[:, :, 1], boxes[:, :, 2], boxes[:, :, 3], w, h, w * h], 2).astype(np.float32)
+    return dict(feats=b["feats"], boxes=boxes, sents=maha_sentences(tag, n), target=maha_targets(tag, n))
