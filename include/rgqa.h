@@ -135,7 +135,12 @@ int rgqa_engine_loss_backward(rgqa_engine* e, const float* target, int ld_target
                               int accumulate, void* stream);
 /* backward from a caller-supplied dL/dlogits [B,num_answers] f32 (autograd integration) */
 int rgqa_engine_backward(rgqa_engine* e, const float* dlogits, int ld, int accumulate, void* stream);
-/* backward from dL/dpooled [B,hidden] f32: LXRTEncoder used under a caller-owned head (tasks/vqa_model.py, nlvr2_model.py) */
+/* backward from dL/dpooled [B,hidden] f32 with row stride ld >= hidden (any alignment): LXRTEncoder used under a caller-owned head
+ * (tasks/vqa_model.py, nlvr2_model.py), and the Mahalanobis scorer (tasks/gqa_maha.py:240-244).  BUTD (arch = 1): pooled is joint_repr = q_repr *
+ * img_repr (butd/butd.py:463), what GQABUTD_maha returns beside the logits; dpooled enters the products in f32.  The answer head above the pooled
+ * vector gets no gradient from this entry: accumulate = 0 writes exact zeros into its range of the arena (BUTD: ans_classifier.0 / .3, bias,
+ * weight_g and weight_v - the tail of the arena), accumulate = 1 leaves it as it is, so rgqa_engine_backward followed by this call with
+ * accumulate = 1 after ONE forward gives the gradient of a loss that reads both outputs.  Honours rgqa_engine_set_input_grads. */
 int rgqa_engine_backward_pooled(rgqa_engine* e, const float* dpooled, int ld, int accumulate, void* stream);
 /* debug / parity: copy a saved activation ("embed_lang", "embed_visn", "l3", "r1", "x2_lang", "x2_visn", "pooled") as f32 */
 int rgqa_engine_get_activation(rgqa_engine* e, const char* name, float* out, size_t cap_elems, void* stream);

@@ -1,4 +1,4 @@
-"""Mirror of the reference's butd/butd.py `GQABUTD(num_answers, dictionary, dropout=True)` (108-221) on the HIP engine
+"""Mirror of the reference's butd/butd.py `GQABUTD(num_answers, dictionary, dropout=True)` (108-221) and `GQABUTD_maha` (355-469) on the HIP engine
 (rgqa_config.arch = 1): same constructor, `tokenize`, `forward(feat, pos, sent, attention=False)` and state_dict keys
 (`w_emb.emb.weight`, `q_enc.rnn.weight_ih_l0`, `att.image_proj.mlp.0.weight_g/_v`, `ans_classifier.3.bias`, ...).
 The module tree only carries parameters (views of the engine's flat arena); GRU, weight-norm projections, the
@@ -96,14 +96,39 @@ class GQABUTD(nn.Module):
             raise RuntimeError("rgqa_amd: inputs must be on the MI355X (device 'cuda'); there is no CPU path")
         toks = self.tokenize(sent).to(feat.device)
         feat, pos = feat.contiguous().float(), pos.contiguous().float()
+        logits, _ = self._forward_both(feat, pos, toks, False)
+        if not attention:
+            return logits
+        return logits, self._attention(feat)
+
+    def _forward_both(self, feat, pos, toks, want_joint):
+        """(logits, joint_repr or None): under enable_grad both come from ONE autograd node, so a gradient arriving at joint_repr reaches the engine as
+        rgqa_engine_backward_pooled; under no_grad they are clones of the engine's buffers"""
         if torch.is_grad_enabled():
             if self._anchor is None or self._anchor.device != feat.device:
                 self.__dict__["_anchor"] = torch.zeros(1, device=feat.device, requires_grad=True)
-            logits, _ = _EngineFunction.apply(self._anchor, self, feat, pos, toks, toks, None, True)
-        else:
-            lg, _ = self._engine_forward(feat, pos, toks, toks, None, train=self.training)
-            logits = lg.clone()
-        if not attention:
-            return logits
+            logits, joint = _EngineFunction.apply(self._anchor, self, feat, pos, toks, toks, None, True)
+            return logits, (joint if want_joint else None)
+        lg, pl = self._engine_forward(feat, pos, toks, toks, None, train=self.training)
+        return lg.clone(), (pl.clone() if want_joint else None)
+
+    def _attention(self, feat):
         B, O = feat.shape[0], feat.shape[1]
-        return logits, self._binding.engine.activation("att", B, O).view(B, O, 1)
+        return self._binding.engine.activation("att", B, O).view(B, O, 1)
+
+
+class GQABUTD_maha(GQABUTD):
+    """Mirror of the reference's `GQABUTD_maha` (butd/butd.py:355-469): the same constructor and state_dict keys as `GQABUTD`; `forward` returns
+    `(logits, joint_repr)` with joint_repr = q_repr * img_repr [B, 1024] (:463-467), what the Mahalanobis test method scores (tasks/gqa_maha.py), or
+    `(logits, att)` with attention=True (:468-469).  `joint_repr.backward(...)` runs the engine's backward from joint_repr
+    (rgqa_engine_backward_pooled): the answer classifier gets no gradient from it."""
+
+    def forward(self, feat, pos, sent, attention=False):
+        if feat.device.type != "cuda":
+            raise RuntimeError("rgqa_amd: inputs must be on the MI355X (device 'cuda'); there is no CPU path")
+        toks = self.tokenize(sent).to(feat.device)
+        feat, pos = feat.contiguous().float(), pos.contiguous().float()
+        logits, joint = self._forward_both(feat, pos, toks, not attention)
+        if not attention:
+            return logits, joint
+        return logits, self._attention(feat)

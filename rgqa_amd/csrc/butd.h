@@ -35,6 +35,9 @@ template <typename T> int kb_input_grad_finish(const T* die, int Dp, const float
                                                int rows, int O, int F, int Pd, hipStream_t s);
 template <typename T> int kb_mul_fwd(const T* a, const T* b, T* out, size_t n, hipStream_t s);
 template <typename T> int kb_mul_relu_bwd(const T* dj, const T* a, const T* b, T* da, T* db, size_t n, hipStream_t s);
+// the backward entry from joint_repr: d [rows, H] f32 with row stride ldd (any ldd >= H, any alignment), a / b = q_repr / img_repr [rows, H] dense;
+// da = a > 0 ? d * b : 0, db = b > 0 ? d * a : 0, formed in f32 from the f32 d and rounded once (k_cast_pad + kb_mul_relu_bwd round d first)
+template <typename T> int kb_joint_entry_bwd(const float* d, int ldd, const T* a, const T* b, T* da, T* db, int rows, int H, hipStream_t s);
 // effective weight of a (weight-normed when g != null) linear: w [N, ldo] (+ transposed wt [K, ldt] when wt != null)
 template <typename T> int kb_wn_eff(const float* v, const float* g, const float* sumsq, T* w, int ldo, T* wt, int ldt, int N, int K, hipStream_t s);
 // gradient of V (and g) from the gradient of the effective weight; plain copy when g == null. partial: >= 256 floats

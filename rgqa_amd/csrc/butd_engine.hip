@@ -361,7 +361,17 @@ public:
         CKB(k_cast_pad<TB>(dl, ldd, dlogits, NAp, B, NA, 1.0f, s));
         return backward_impl(accumulate, s);
     }
-    int backward_pooled(const float*, int, int, hipStream_t) override { rgqa_set_error("backward_pooled: not available for the BUTD engine"); return RGQA_ERR_ARG; }
+    // backward from dL/djoint_repr (the `pooled` output of forward; butd.py:463 joint_repr = q_repr * img_repr, what GQABUTD_maha returns beside the
+    // logits): everything below the classifier, which gets no gradient from here - exact zeros (accumulate = 0) or left as it is (accumulate = 1)
+    int backward_pooled(const float* dpooled, int ld, int accumulate, hipStream_t s) override {
+        RGQA_REQUIRE(have_fwd, "backward_pooled: no forward pass recorded");
+        RGQA_REQUIRE(G != nullptr && dpooled != nullptr, "backward_pooled: null gradient arena / dpooled");
+        RGQA_REQUIRE(ld >= H, "backward_pooled: ld %d < hidden %d", ld, H);
+        if (!accumulate) CKB(rgqa_check_hip(hipMemsetAsync(G + c0.b, 0, sizeof(float) * (arena_elems - c0.b), s), "zero classifier grads"));
+        CKB(backward_begin(accumulate, s));
+        CKB(kb_joint_entry_bwd<TB>(dpooled, ld, QRb, IRb, dQR, dIR, B, H, s));
+        return backward_joint(accumulate, false, s);
+    }
 
     // Weight gradients.  Low-precision engines, no accumulation: every layer's problem is COLLECTED while the gradient flows back (their operands
     // live in buffers of their own until the end of the pass) and ONE grouped TN launch computes them all - longest contraction first, the bias
@@ -417,18 +427,30 @@ public:
         else return kb_input_grad_finish<TB>(dIE, Dp, att, dIP, H, (const TB*)effp(ip) + F, ip.kp, 1, dfeats_out, dboxes_out, B * O, O, F, Pd, s);
     }
 
-    int backward_impl(int accumulate, hipStream_t s) {
-        const DropCfg nd = make_drop(0.f, 0, 0);
-        const TB* q = Hb + (size_t)L * B * H;
+    int backward_begin(int accumulate, hipStream_t s) {
         if (!accumulate) CKB(rgqa_check_hip(hipMemsetAsync(G + emb, 0, sizeof(float) * (size_t)cfg.vocab_size * E, s), "zero embedding grad"));
         wg_collect = LP && !accumulate;
         memset(&wg, 0, sizeof wg); wg.drop = make_drop(0.f, 0, 0);
+        return RGQA_OK;
+    }
+    // the logits entry: the classifier, then everything below joint_repr
+    int backward_impl(int accumulate, hipStream_t s) {
+        const DropCfg nd = make_drop(0.f, 0, 0);
+        CKB(backward_begin(accumulate, s));
         // classifier
         CKB(wgrad(dlogits, NAp, C1b, 2 * H, B, c3, accumulate, s));
         CKB(gemm_dgrad(dlogits, NAp, B, c3, dC1, 2 * H, EPI_DRELU_DROP, C1b, 2 * H, drop_raw(cfg.hidden_dropout), s));
         CKB(wgrad(dC1, 2 * H, Jb, H, B, c0, accumulate, s));
         CKB(gemm_dgrad(dC1, 2 * H, B, c0, dJ, H, EPI_BIAS, nullptr, 0, nd, s));
         CKB(kb_mul_relu_bwd<TB>(dJ, QRb, IRb, dQR, dIR, (size_t)B * H, s));
+        return backward_joint(accumulate, true, s);
+    }
+    // Both entries from here: dQR / dIR (the gradients of the two factors of joint_repr) down to the word table and the inputs.  head = false
+    // (backward_pooled): the classifier layers c0 / c3 - the last two of `lins`, so the last two descriptors and the last blocks of the grouped
+    // weight-norm launch - have collected no weight-gradient problem and their dW scratch is unwritten: the launch stops short of them.
+    int backward_joint(int accumulate, bool head, hipStream_t s) {
+        const DropCfg nd = make_drop(0.f, 0, 0);
+        const TB* q = Hb + (size_t)L * B * H;
         // projections
         CKB(wgrad(dQR, H, q, H, B, qproj, accumulate, s));
         CKB(gemm_dgrad(dQR, H, B, qproj, dq, H, EPI_BIAS, nullptr, 0, nd, s));
@@ -480,7 +502,8 @@ public:
         }
         if (wg_collect) {
             CKB(tn_gemm(wg, s));
-            CKB(kb_wn_backward_group(wn_dev, (int)wn_host.size(), wn_blocks, wn_partial, s));
+            const int nl = (int)wn_host.size() - (head ? 0 : 2);
+            CKB(kb_wn_backward_group(wn_dev, nl, head ? wn_blocks : wn_host[nl].blk0, wn_partial, s));
             wg_collect = false;
         }
         // the one gradient segment of this engine (the whole arena: every weight gradient lands in the last launches of the pass) is final: the

@@ -342,6 +342,50 @@ __global__ void mul_relu_bwd_kernel(const T* __restrict__ dj, const T* __restric
     }
 }
 
+// The backward pass's entry from joint_repr (rgqa_engine_backward_pooled): d = dL/djoint [rows, H] in f32, row stride ldd (the caller's), so the
+// incoming gradient is never rounded to the engine's gradient type before the products - da = a > 0 ? d * b : 0, db = b > 0 ? d * a : 0 in f32,
+// rounded once.  One launch in place of k_cast_pad + mul_relu_bwd_kernel.  VEC: 8 elements per thread with 16-byte accesses (H % 8 == 0,
+// ldd % 4 == 0, d 16-byte aligned: the host wrapper checks); otherwise one element per thread.
+__device__ __forceinline__ void load8(const float* p, float v[8]) { load4(p, v); load4(p + 4, v + 4); }
+__device__ __forceinline__ void load8(const bf16_t* p, float v[8]) {
+    const bf16x8 t = *reinterpret_cast<const bf16x8*>(p);
+#pragma unroll
+    for (int i = 0; i < 8; ++i) v[i] = (float)t[i];
+}
+__device__ __forceinline__ void load8(const sf32* p, float v[8]) { sf_load8(p, v); }
+__device__ __forceinline__ void store8(float* p, const float v[8]) { store4(p, v); store4(p + 4, v + 4); }
+__device__ __forceinline__ void store8(bf16_t* p, const float v[8]) {
+    bf16x8 t;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) t[i] = (bf16_t)v[i];
+    *reinterpret_cast<bf16x8*>(p) = t;
+}
+__device__ __forceinline__ void store8(sf32* p, const float v[8]) { sf_store8(p, v); }
+template <typename T, bool VEC>
+__global__ __launch_bounds__(256) void joint_entry_bwd_kernel(const float* __restrict__ d, long ldd, const T* __restrict__ a, const T* __restrict__ b,
+                                                              T* __restrict__ da, T* __restrict__ db, int rows, int H) {
+    if (VEC) {
+        const int hq = H >> 3;
+        const size_t nq = (size_t)rows * hq;
+        for (size_t q = (size_t)blockIdx.x * 256 + threadIdx.x; q < nq; q += (size_t)gridDim.x * 256) {
+            const size_t r = q / hq, i = r * H + (q - r * hq) * 8;
+            float g[8], x[8], y[8], u[8], w[8];
+            load8(d + r * ldd + (q - r * hq) * 8, g); load8(a + i, x); load8(b + i, y);
+#pragma unroll
+            for (int k = 0; k < 8; ++k) { u[k] = x[k] > 0.f ? g[k] * y[k] : 0.f; w[k] = y[k] > 0.f ? g[k] * x[k] : 0.f; }
+            store8(da + i, u); store8(db + i, w);
+        }
+    } else {
+        const size_t n = (size_t)rows * H;
+        for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) {
+            const size_t r = i / H;
+            const float g = d[r * ldd + (i - r * H)], x = ld_elem(a + (i)), y = ld_elem(b + (i));
+            st_elem(da + (i), x > 0.f ? g * y : 0.f);
+            st_elem(db + (i), y > 0.f ? g * x : 0.f);
+        }
+    }
+}
+
 // ---------------------------------------------------------------- weight norm (scalar g): W = g * V / ||V||_F
 // writes the effective weight [N, ldo] (zero padded past K) and, when wt != null, its transpose [K.., ldt]
 template <typename T>
@@ -622,6 +666,14 @@ template <typename T> int kb_mul_relu_bwd(const T* dj, const T* a, const T* b, T
     hipLaunchKernelGGL(mul_relu_bwd_kernel<T>, GRID1(n), dim3(256), 0, s, dj, a, b, da, db, n);
     RGQA_LAUNCH_CHECK("mul_relu_bwd_kernel"); return RGQA_OK;
 }
+template <typename T> int kb_joint_entry_bwd(const float* d, int ldd, const T* a, const T* b, T* da, T* db, int rows, int H, hipStream_t s) {
+    RGQA_REQUIRE(rows > 0 && H > 0 && ldd >= H, "butd joint entry: rows %d, H %d, ld %d", rows, H, ldd);
+    // (a, b, da, db are workspace rows of H elements: 256-byte aligned buffers, H % 8 == 0 keeps every group of 8 inside a row and, split f32, a line)
+    const bool vec = (H & 7) == 0 && (ldd & 3) == 0 && (reinterpret_cast<uintptr_t>(d) & 15) == 0;
+    if (vec) hipLaunchKernelGGL((joint_entry_bwd_kernel<T, true>), GRID1((size_t)rows * (H >> 3)), dim3(256), 0, s, d, (long)ldd, a, b, da, db, rows, H);
+    else hipLaunchKernelGGL((joint_entry_bwd_kernel<T, false>), GRID1((size_t)rows * H), dim3(256), 0, s, d, (long)ldd, a, b, da, db, rows, H);
+    RGQA_LAUNCH_CHECK("joint_entry_bwd_kernel"); return RGQA_OK;
+}
 template <typename T> int kb_wn_eff(const float* v, const float* g, const float* sumsq, T* w, int ldo, T* wt, int ldt, int N, int K, hipStream_t s) {
     const int kk = ldo > K ? ldo : K;
     hipLaunchKernelGGL(wn_eff_kernel<T>, dim3(cdiv(kk, 32), cdiv(wt ? (ldt > N ? ldt : N) : N, 32)), dim3(256), 0, s, v, g, sumsq, w, ldo, wt, ldt, N, K);
@@ -650,6 +702,7 @@ int kb_wn_bwd(const float* dw, int lddw, const float* v, const float* g, const f
     template int kb_input_grad_finish<T>(const T*, int, const float*, const T*, int, const T*, long, long, float*, float*, int, int, int, int, hipStream_t); \
     template int kb_mul_fwd<T>(const T*, const T*, T*, size_t, hipStream_t);                                                             \
     template int kb_mul_relu_bwd<T>(const T*, const T*, const T*, T*, T*, size_t, hipStream_t);                                          \
+    template int kb_joint_entry_bwd<T>(const float*, int, const T*, const T*, T*, T*, int, int, hipStream_t);                            \
     template int kb_wn_eff<T>(const float*, const float*, const float*, T*, int, T*, int, int, int, hipStream_t);
 INST(float)
 INST(bf16_t)

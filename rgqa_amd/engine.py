@@ -277,7 +277,9 @@ class Engine:
         self._seg_sumsq_valid = self._seg_sumsq is not None
 
     def backward_pooled(self, dpooled, accumulate=False):
-        dpooled = dpooled.contiguous().float()
+        """dpooled [B, H]: an f32 view with unit inner stride goes to the engine as it is (its row stride is the call's `ld`)."""
+        if dpooled.dtype != torch.float32 or dpooled.dim() != 2 or dpooled.stride(1) != 1 or dpooled.stride(0) < dpooled.shape[1]:
+            dpooled = dpooled.contiguous().float()
         check(self.lib.rgqa_engine_backward_pooled(self.h, ptr(dpooled), dpooled.stride(0), 1 if accumulate else 0, _stream()))
         self._wev_refs.pop("bwd", None)
 

@@ -13,7 +13,8 @@ backbones:
     featsPt = torch.add(feats.data, (torch.ge(feats.grad, 0).float() - 0.5) * 2, alpha=-noise)             :115-121   sign_step
     the whole batch step: forward, loss gradient, input gradients, perturbed inputs, second forward, score  :97-131    odin_scores
 
-and the Mahalanobis method (tasks/gqa_maha.py) for LXMERT and UNITER, on the pooled vector `GQAModel_maha` / `GQAUNITER_maha` return:
+and the Mahalanobis method (tasks/gqa_maha.py) for all three backbones, on the pooled vector `GQAModel_maha` / `GQAUNITER_maha` return and on the
+`joint_repr` of `GQABUTD_maha`:
 
     mean[j] = mean of the pooled rows of the samples with target[i][j] != 0; precision = pinvh(covariance)  :130-183   MahaEstimator, maha_sample_estimator
     gaussian_score[b, c] = -0.5 (x_b - mean_c)^T precision (x_b - mean_c); .max(1)                          :228-239   maha_score_rows
@@ -233,21 +234,21 @@ class MahaEstimator:
 
 
 def _maha_model_check(model):
-    from .butd.butd import GQABUTD
-    if isinstance(model, GQABUTD):
-        raise NotImplementedError("maha: the BUTD backbone is not supported: the reference's GQABUTD_maha scores `joint_repr`, and the BUTD engine has no "
-                                  "backward from it (no backward_pooled); use GQAModel_maha or GQAUNITER_maha")
+    from .butd.butd import GQABUTD, GQABUTD_maha
+    if isinstance(model, GQABUTD) and not isinstance(model, GQABUTD_maha):
+        raise NotImplementedError("maha: a plain BUTD GQABUTD returns no `joint_repr`, the vector the reference's Mahalanobis method scores on this backbone; "
+                                  "build the model as GQABUTD_maha (same constructor and state_dict keys)")
 
 
 def _maha_forward(model, feats, boxes, sent):
     out = model(feats, boxes, sent)
     if not (isinstance(out, tuple) and len(out) == 2):
-        raise ValueError("maha: the model must return (logit, pooled) as GQAModel_maha / GQAUNITER_maha do")
+        raise ValueError("maha: the model must return (logit, pooled) as GQAModel_maha / GQAUNITER_maha / GQABUTD_maha do")
     return out[1]
 
 
 def maha_sample_estimator(model, batches):
-    """gqa_maha.py:130-189 through a drop-in `GQAModel_maha` / `GQAUNITER_maha`: batches yields (feats, boxes, sent, target) with the UQ column of
+    """gqa_maha.py:130-189 through a drop-in `GQAModel_maha` / `GQAUNITER_maha` / `GQABUTD_maha`: batches yields (feats, boxes, sent, target) with the UQ column of
     target already dropped (:141).  Runs under eval() and no_grad, restores the model's mode, returns the MahaPack."""
     _maha_model_check(model)
     was_training = model.training
@@ -306,14 +307,15 @@ def maha_dpooled(rows, pack):
 
 
 def maha_scores(model, feats, boxes, sent, pack, noise=0.0):
-    """One batch of the reference's Mahalanobis scorer (gqa_maha.py:223-270) for `GQAModel_maha` or `GQAUNITER_maha` (drop-in classes): forward,
+    """One batch of the reference's Mahalanobis scorer (gqa_maha.py:223-270) for `GQAModel_maha`, `GQAUNITER_maha` or `GQABUTD_maha` (drop-in classes): forward,
     `maha_score_rows`, `maha_dpooled`, backward from the pooled output with input gradients, two `sign_step`s, a second forward under no_grad on the
     perturbed inputs, `maha_score_rows`.  Returns MahaScores(score, label, pooled, feats_pt, boxes_pt): score / label = noised_gaussian_score.max(1)
     of the SECOND pass, its pooled vectors, and the perturbed inputs.  (`--temperature` is passed by the reference's script and never read.)
 
-    `model.training` is honoured as the caller set it (the reference scores LXMERT / UNITER in eval()); the pass never runs the data-parallel gradient
-    exchange.  Afterwards the parameters' `.grad` hold the scoring pass's gradients, as after the reference's `loss.backward()`.  BUTD raises
-    NotImplementedError."""
+    `model.training` is honoured as the caller set it (the reference scores LXMERT / UNITER in eval() and BUTD in train() with dropout=False,
+    gqa_maha.py:205-206); the pass never runs the data-parallel gradient exchange.  Afterwards the parameters' `.grad` hold the scoring pass's
+    gradients, as after the reference's `loss.backward()` (BUTD: exact zeros for the answer classifier, which joint_repr does not pass through).  A
+    plain `GQABUTD` (no `joint_repr`) raises NotImplementedError."""
     from .lxrt.modeling import scoring_pass
     _maha_model_check(model)
     f = feats.detach().contiguous().float().requires_grad_(True)

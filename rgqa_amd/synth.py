@@ -222,3 +222,37 @@ def maha_case(backbone, part):
         w, h = boxes[:, :, 2] - boxes[:, :, 0], boxes[:, :, 3] - boxes[:, :, 1]
         boxes = np.stack([boxes[:, :, 0], boxes[:, :, 1], boxes[:, :, 2], boxes[:, :, 3], w, h, w * h], 2).astype(np.float32)
     return dict(feats=b["feats"], boxes=boxes, sents=maha_sentences(tag, n), target=maha_targets(tag, n))
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# The BUTD Mahalanobis fixture (tests/golden/g14_butd_maha.npz, tools/gen_g14_butd_maha.py): the G7 batch (BUTD_SENTS, 36 regions, 23 answers)
+# through the reference's GQABUTD_maha, scored against a synthetic class-mean / precision pair at H = 1024.
+BUTD_MAHA_NC, BUTD_MAHA_H, BUTD_MAHA_NOISE = 23, 1024, 1e-4
+
+
+def butd_maha_fill(filled):
+    """The G7 BUTD weights (tests/test_oracle_golden.py butd_fill) at unit gain: every weight_g times 8, the GRU weight matrices and the word table
+    times 3.  Under the G7 filler joint_repr = q_repr * img_repr barely moves between samples (max 3e-3, rows 1e-3 apart) and the gradients w.r.t.
+    the inputs are near 1e-9; with these factors q_repr and img_repr reach 1.0 and 0.4, joint_repr 0.25 with rows 0.2 apart, and three quarters of it
+    are the exact zeros of the two ReLUs.  (weight_g times 16 and more sharpens the attention over the regions until the input gradients sit on a few
+    regions and the sign mask of tests/test_gpu_odin.py keeps under a quarter of them.)"""
+    out = {}
+    for k, v in filled.items():
+        v = np.asarray(v, dtype=np.float32)
+        if k.endswith("weight_g"):
+            v = (v * np.float32(8.0)).astype(np.float32)
+        elif k in ("q_enc.rnn.weight_ih_l0", "q_enc.rnn.weight_hh_l0", "w_emb.emb.weight"):
+            v = (v * np.float32(3.0)).astype(np.float32)
+        out[k] = v
+    return out
+
+
+def butd_maha_precision(H=BUTD_MAHA_H):
+    """f64 [H, H], symmetric positive definite: M^T M / H + 0.1 I with M uniform in [-1, 1) (eigenvalues in about [0.1, 1.4]: condition 14)"""
+    M = uniform("g14.butd.precision", (H, H), -1.0, 1.0).astype(np.float64)
+    return M.T @ M / H + 0.1 * np.eye(H)
+
+
+def butd_maha_mean(scale, NC=BUTD_MAHA_NC, H=BUTD_MAHA_H):
+    """f32 [NC, H] class means, scale * U[0, 1): non-negative like joint_repr itself"""
+    return (np.float32(scale) * uniform("g14.butd.mean", (NC, H), 0.0, 1.0)).astype(np.float32)

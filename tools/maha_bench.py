@@ -1,5 +1,5 @@
 """Per-batch time of the Mahalanobis scorer (rgqa_amd.scoring.maha_scores; the reference's tasks/gqa_maha.py:223-270) through the drop-in
-`GQAModel_maha` / `GQAUNITER_maha`, full configuration, NC = 1842, at the reference's test batch (32, scripts/*/test/maha.sh) and at 256.  Legs
+`GQAModel_maha` / `GQAUNITER_maha` / `GQABUTD_maha` (hidden 1024, built as tools/odin_bench.py builds its BUTD model), full configuration, NC = 1842, at the reference's test batch (32, scripts/*/test/maha.sh) and at 256.  Legs
 alternate in one process after a warm-up, each window bracketed by device synchronisation:
 
     fwd        the second forward (no_grad)
@@ -10,7 +10,7 @@ alternate in one process after a warm-up, each window bracketed by device synchr
     pasted_loops   their two class loops and the loss statements alone, on a pooled vector (what `scorer` replaces)
     update     MahaEstimator.update on one batch (the estimator's per-batch cost next to `fwd`; reported at every batch size)
 
-    timeout 900 python tools/maha_bench.py [--backbones lxmert,uniter] [--precisions bf16x3_fwd] [--batches 32,256] [--only-leg fused]
+    timeout 900 python tools/maha_bench.py [--backbones lxmert,uniter,butd] [--precisions bf16x3_fwd] [--batches 32,256] [--only-leg fused]
 
 Prints one JSON line per (backbone, precision, batch): median ms per batch of each leg over the windows.  Not part of bench.py."""
 import argparse
@@ -41,16 +41,24 @@ def make_model(backbone, precision):
     if backbone == "lxmert":
         from rgqa_amd.tasks.gqa_model import GQAModel_maha
         return GQAModel_maha(NC, max_seq_length=20, model_args=margs).cuda().eval()
-    from rgqa_amd.uniter.uniter import GQAUNITER_maha
-    return GQAUNITER_maha(NC, model_args=margs).cuda().eval()
+    if backbone == "uniter":
+        from rgqa_amd.uniter.uniter import GQAUNITER_maha
+        return GQAUNITER_maha(NC, model_args=margs).cuda().eval()
+    from rgqa_amd.butd.butd import GQABUTD_maha
+    from rgqa_amd.butd.preprocess import Dictionary
+    d = Dictionary()
+    for i in range(3000):
+        d.add_word(OB.WORDS[i] if i < len(OB.WORDS) else "w%d" % i)
+    return GQABUTD_maha(NC, d, dropout=False, precision=precision).cuda().train()      # the reference scores BUTD in train() (gqa_maha.py:205-206)
 
 
-def make_pack(model, feats, boxes, sent, H=768, seed=0):
-    """class means scattered around the model's own pooled vectors, a covariance of condition 1e2 with random axes"""
+def make_pack(model, feats, boxes, sent, seed=0):
+    """class means scattered around the model's own pooled vectors (H = 768; BUTD: joint_repr, H = 1024), a covariance of condition 1e2 with random axes"""
     from rgqa_amd import scoring
     rng = np.random.RandomState(seed)
     with torch.no_grad():
         x = model(feats, boxes, sent)[1].cpu().numpy()
+    H = x.shape[1]
     Q, _ = np.linalg.qr(rng.standard_normal((H, H)))
     lam = np.exp(rng.uniform(np.log(1e-4), np.log(1e-2), H))
     mean = (x[rng.randint(0, len(x), NC)] + 0.05 * rng.standard_normal((NC, H))).astype(np.float32)
