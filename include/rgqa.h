@@ -133,6 +133,15 @@ int rgqa_engine_forward(rgqa_engine* e, const float* feats, const float* boxes, 
  * grad_scale multiplies dL/dlogits (1 for a plain step). accumulate = 0 overwrites the gradient arena. */
 int rgqa_engine_loss_backward(rgqa_engine* e, const float* target, int ld_target, float* loss_out, float grad_scale,
                               int accumulate, void* stream);
+/* The train step of the energy fine-tuning (tasks/gqa_energy.py:117-145, run/gqa_energy_finetune.bash): rgqa_op_energy_loss (below) on the last
+ * forward's logits + full backward into the grad arena, every precision, every backbone.  target [B, ld_target >= num_answers] f32; ood_flag[b * ld_flag]
+ * != 0 marks row b unanswerable - pass target + num_answers and ld_target for a target that carries the UQ column, nothing is copied.  loss3 (3 floats:
+ * total, base loss, regulariser), energy [B], label [B] int64: device buffers, each may be NULL.  The f32 dlogits are written where
+ * rgqa_engine_loss_backward writes them and take the same path from there: with weight = 0 and mce = 0 the gradient arena has the bits that call
+ * leaves, and after any call the bits of rgqa_engine_backward on the operator's dlogits.  Honours rgqa_engine_set_input_grads. */
+int rgqa_engine_energy_loss_backward(rgqa_engine* e, const float* target, int ld_target, const float* ood_flag, int ld_flag, int mce, float weight,
+                                     float m_in, float m_out, float grad_scale, float* loss3, float* energy, int64_t* label, int accumulate,
+                                     void* stream);
 /* backward from a caller-supplied dL/dlogits [B,num_answers] f32 (autograd integration) */
 int rgqa_engine_backward(rgqa_engine* e, const float* dlogits, int ld, int accumulate, void* stream);
 /* backward from dL/dpooled [B,hidden] f32 with row stride ld >= hidden (any alignment): LXRTEncoder used under a caller-owned head
@@ -399,6 +408,21 @@ int rgqa_op_attention_rows(const void* q, int ldq, const void* kv, int ldkv, con
 int rgqa_op_attention_rows_bwd(const void* q, int ldq, const void* kv, int ldkv, const int* cu_q, const int* cu_k, const float* mask, const float* lse,
                                const void* dout, void* dq, void* dkv, int B, int nh, int Lq, int Lk, int dtype, int impl, void* stream);
 int rgqa_op_bce(const float* logits, const float* target, float* loss, float* dlogits, int B, int NA, void* stream);
+/* The loss head of the energy fine-tuning (tasks/gqa_energy.py:122-138, :144-145; rgqa_amd/csrc/energy_loss.hip), one pass per row:
+ *   base  = BCEWithLogitsLoss()(logit, target) * NA, E_b = log(1 + exp(logit_b)).sum()                   (mce = 0; :133-135)
+ *         = CrossEntropyLoss()(logit, target.max(1)[1]) * NA, E_b = logsumexp(logit_b)                    (mce != 0, --mceLoss; :128-131)
+ *   reg   = weight * mean over ID rows of relu(-E_b - m_in)^2 + weight * mean over OOD rows of relu(m_out + E_b)^2      (:137-138, weight 0.1 there)
+ *   label = sigmoid(logit).max(1)[1] (first maximum of the f32 sigmoid values, as rgqa_score_rows), energy = E      (:144-145)
+ *   dlogits = d (base + reg) / d logit * grad_scale, f32 [B, ldd >= NAp >= NA], columns NA .. NAp exact zeros
+ * Row b is OOD when ood_flag[b * ld_flag] != 0 (for a target with the UQ column: target + NA, ld_target).  The mean over an empty subset is NaN as
+ * torch's is (loss3[0] and loss3[2] are NaN then); dlogits stay finite and carry the base loss and the other subset's term.  Outputs loss3 (3 floats:
+ * base + reg, base, reg), dlogits, energy [B], label [B] may each be NULL; loss3 needs `scratch` of rgqa_op_energy_loss_scratch_floats(B) floats
+ * (any content).  No float atomics: results repeat bit for bit and do not depend on the operands' alignment; with weight = 0 and mce = 0, and in every
+ * row whose hinge is inactive, dlogits has the bits of rgqa_op_bce.  Logits above 88.7 overflow exp() as they do in the reference. */
+int rgqa_op_energy_loss_scratch_floats(int B, size_t* out);
+int rgqa_op_energy_loss(const float* logits, int ld, const float* target, int ld_target, const float* ood_flag, int ld_flag, int B, int NA, int NAp,
+                        int mce, float weight, float m_in, float m_out, float grad_scale, float* loss3, float* dlogits, int ldd, float* energy,
+                        int64_t* label, float* scratch, void* stream);
 
 #ifdef __cplusplus
 }

@@ -356,6 +356,15 @@ public:
         CKB(k_cast_pad<TB>(dl32, NAp, dlogits, NAp, B, NAp, 1.0f, s));
         return backward_impl(accumulate, s);
     }
+    int energy_loss_backward(const float* target, int ldt, const float* ood_flag, int ldf, const EnergyLossCfg& c, float grad_scale, float* loss3, float* energy,
+                             int64_t* label, int accumulate, hipStream_t s) override {
+        RGQA_REQUIRE(have_fwd && G != nullptr, "energy_loss_backward: no forward pass recorded / no gradient arena");
+        float* dl32 = dwscr;
+        RGQA_REQUIRE(k_energy_loss_scratch_floats(B) <= partial_floats, "energy_loss_backward: batch %d exceeds the scratch", B);
+        CKB(k_energy_loss(logits, NAp, target, ldt, ood_flag, ldf, B, NA, NAp, c, grad_scale, loss3, dl32, NAp, energy, label, partial, s));      // (partial: the column-sum scratch, free until the backward pass below)
+        CKB(k_cast_pad<TB>(dl32, NAp, dlogits, NAp, B, NAp, 1.0f, s));
+        return backward_impl(accumulate, s);
+    }
     int backward(const float* dl, int ldd, int accumulate, hipStream_t s) override {
         RGQA_REQUIRE(have_fwd && G != nullptr && dl != nullptr, "backward: no forward pass recorded / null argument");
         CKB(k_cast_pad<TB>(dl, ldd, dlogits, NAp, B, NA, 1.0f, s));

@@ -141,6 +141,13 @@ int rgqa_engine_loss_backward(rgqa_engine* e, const float* target, int ldt, floa
     RGQA_REQUIRE(target != nullptr, "loss_backward: null target");
     return e->impl->loss_backward(target, ldt, loss_out, grad_scale, accumulate, S(stream));
 }
+int rgqa_engine_energy_loss_backward(rgqa_engine* e, const float* target, int ldt, const float* ood_flag, int ld_flag, int mce, float weight, float m_in, float m_out,
+                                     float grad_scale, float* loss3, float* energy, int64_t* label, int accumulate, void* stream) {
+    NEED(e);
+    RGQA_REQUIRE(target != nullptr && ood_flag != nullptr, "energy_loss_backward: null target / flag pointer");
+    const EnergyLossCfg c = {mce ? 1 : 0, weight, m_in, m_out};
+    return e->impl->energy_loss_backward(target, ldt, ood_flag, ld_flag, c, grad_scale, loss3, energy, label, accumulate, S(stream));
+}
 int rgqa_engine_backward(rgqa_engine* e, const float* dlogits, int ld, int accumulate, void* stream) {
     NEED(e);
     return e->impl->backward(dlogits, ld, accumulate, S(stream));
@@ -448,6 +455,16 @@ int rgqa_odin_dlogits(const float* logits, int ld, const int64_t* label, const f
     return k_odin_dlogits(logits, ld, label, max_score, B, NA, NAp, dlogits, ldd, loss, S(stream));
 }
 int rgqa_sign_step(const float* x, const float* grad, float noise, float* out, size_t n, void* stream) { return k_sign_step(x, grad, noise, out, n, S(stream)); }
+int rgqa_op_energy_loss_scratch_floats(int B, size_t* out) {
+    RGQA_REQUIRE(B > 0 && out != nullptr, "op_energy_loss_scratch_floats: bad argument");
+    *out = k_energy_loss_scratch_floats(B);
+    return RGQA_OK;
+}
+int rgqa_op_energy_loss(const float* logits, int ld, const float* target, int ld_target, const float* ood_flag, int ld_flag, int B, int NA, int NAp, int mce, float weight,
+                        float m_in, float m_out, float grad_scale, float* loss3, float* dlogits, int ldd, float* energy, int64_t* label, float* scratch, void* stream) {
+    const EnergyLossCfg c = {mce ? 1 : 0, weight, m_in, m_out};
+    return k_energy_loss(logits, ld, target, ld_target, ood_flag, ld_flag, B, NA, NAp, c, grad_scale, loss3, dlogits, ldd, energy, label, scratch, S(stream));
+}
 int rgqa_op_bce(const float* logits, const float* target, float* loss, float* dlogits, int B, int NA, void* stream) {
     return k_bce_fwd_bwd(logits, NA, target, NA, loss, dlogits, NA, B, NA, NA, 1.0f, S(stream));
 }

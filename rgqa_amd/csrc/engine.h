@@ -107,6 +107,10 @@ public:
     virtual int forward(const float* feats, const float* boxes, const int64_t* ids, const int64_t* seg, const int64_t* mask,
                         float* pooled_out, float* logits_out, int ld_logits, int train, uint64_t seed, hipStream_t s) = 0;
     virtual int loss_backward(const float* target, int ldt, float* loss_out, float grad_scale, int accumulate, hipStream_t s) = 0;
+    // the loss head of the energy fine-tuning (tasks/gqa_energy.py:122-138, :144-145; energy_loss.hip) + backward: the f32 dlogits land where loss_backward
+    // writes them and take the same path from there.  loss3 {total, base, regulariser}, energy [B], label [B]: caller's device buffers, each may be null
+    virtual int energy_loss_backward(const float* target, int ldt, const float* ood_flag, int ldf, const EnergyLossCfg& c, float grad_scale, float* loss3, float* energy,
+                                     int64_t* label, int accumulate, hipStream_t s) = 0;
     virtual int backward(const float* dlogits, int ldd, int accumulate, hipStream_t s) = 0;
     virtual int backward_pooled(const float* dpooled, int ld, int accumulate, hipStream_t s) = 0;
     // gradient-arena ranges in the order backward finishes them (for overlapping the DP exchange with backward)

@@ -1146,6 +1146,17 @@ public:
         CKP(PC_OTHER, k_cast_pad<TB>(dl32, NAp, dlogits, NAp, B, NAp, 1.0f, s));
         return backward_impl(accumulate, s);
     }
+    int energy_loss_backward(const float* target, int ldt, const float* ood_flag, int ldf, const EnergyLossCfg& c, float grad_scale, float* loss3, float* energy,
+                             int64_t* label, int accumulate, hipStream_t s) override {
+        RGQA_REQUIRE(have_fwd, "energy_loss_backward: no forward pass recorded");
+        RGQA_REQUIRE(G != nullptr, "energy_loss_backward: no gradient arena bound");
+        prof_block = PB_HEAD;
+        float* dl32 = part;   // as loss_backward: [B, NAp] f32, the row shares of the loss behind it
+        RGQA_REQUIRE((size_t)B * NAp + k_energy_loss_scratch_floats(B) <= part_floats, "energy_loss_backward: batch %d exceeds the scratch", B);
+        CKP(PC_OTHER, k_energy_loss(logits, NAp, target, ldt, ood_flag, ldf, B, cfg.num_answers, NAp, c, grad_scale, loss3, dl32, NAp, energy, label, part + (size_t)B * NAp, s));
+        CKP(PC_OTHER, k_cast_pad<TB>(dl32, NAp, dlogits, NAp, B, NAp, 1.0f, s));
+        return backward_impl(accumulate, s);
+    }
     int backward(const float* dl, int ldd, int accumulate, hipStream_t s) override {
         RGQA_REQUIRE(have_fwd, "backward: no forward pass recorded");
         RGQA_REQUIRE(G != nullptr && dl != nullptr, "backward: null gradient arena / dlogits");

@@ -181,6 +181,22 @@ int k_visn_combine_bwd(const T* dout, int lddo, const T* zf, int ldz, const floa
 // loss = mean_b sum_n BCEWithLogits(z, t)  (= BCEWithLogitsLoss() * NA, gqa_conf.py:197-198); dz = (sigmoid(z)-t)/B * grad_scale
 int k_bce_fwd_bwd(const float* logits, int ldl, const float* target, int ldt, float* loss_out, float* dlogits, int lddl, int B, int NA, int NAp, float grad_scale, hipStream_t s,
                   float* row_scratch = nullptr /* B floats: the loss is then folded in a fixed order (no float atomics) */);
+#if defined(__HIPCC__)
+// The element formulas of the BCE head, shared by bce_kernel (loss.hip) and energy_loss_kernel (energy_loss.hip): a row of the energy loss whose
+// regulariser coefficient is an exact zero gets the dlogits bits of bce_kernel.
+__device__ __forceinline__ float bce_term(float x, float y) { return fmaxf(x, 0.f) - x * y + log1pf(__expf(-fabsf(x))); }
+__device__ __forceinline__ float bce_sigmoid(float x) { return 1.f / (1.f + __expf(-x)); }
+// log(1 + exp(x)) as the reference writes it (tasks/gqa_energy.py:135,185): +inf above x = 88.7, as torch's (score.hip, energy_loss.hip)
+__device__ __forceinline__ float softplus_naive(float x) { return logf(1.0f + expf(x)); }
+#endif
+
+// ---- energy_loss.hip: the loss head of the energy fine-tuning (tasks/gqa_energy.py:122-138, :144-145) in one pass per row
+struct EnergyLossCfg { int mce; float weight, m_in, m_out; };     // mce: --mceLoss (cross entropy x NA, E = logsumexp) instead of BCE x NA (E = sum softplus)
+size_t k_energy_loss_scratch_floats(int B);
+// ood_flag[b * ldf] != 0: row b is unanswerable (the caller passes target + NA with the target's own stride).  Outputs, each may be null: loss3 = {total, base,
+// regulariser} (needs `scratch`, k_energy_loss_scratch_floats(B) floats), dlogits [B, NAp] f32 (columns NA .. NAp exact zeros), energy [B], label [B].
+int k_energy_loss(const float* logits, int ld, const float* target, int ldt, const float* ood_flag, int ldf, int B, int NA, int NAp, const EnergyLossCfg& c, float grad_scale,
+                  float* loss3, float* dlogits, int ldd, float* energy, int64_t* label, float* scratch, hipStream_t s);
 
 // ---- optim.hip
 int k_sumsq(const float* g, size_t n, float* partial /* >= 1025 floats, any content ([1024] = ticket word, zeroed on the stream by the call) */, float* out_sumsq, int accumulate_into_out, hipStream_t s);

@@ -14,8 +14,8 @@ __global__ __launch_bounds__(256) void bce_kernel(const float* __restrict__ z, i
         float g = 0.f;
         if (n < NA) {
             const float x = z[(size_t)b * ldl + n], y = t[(size_t)b * ldt + n];
-            acc += fmaxf(x, 0.f) - x * y + log1pf(__expf(-fabsf(x)));
-            const float sg = 1.f / (1.f + __expf(-x));
+            acc += bce_term(x, y);
+            const float sg = bce_sigmoid(x);
             g = (sg - y) * inv_b * gscale;
         }
         if (dz) dz[(size_t)b * lddl + n] = g;   // padded columns get exact zeros (they feed K-padded GEMMs)

@@ -10,8 +10,6 @@
 // as on the reference's CPU path.
 #include "kernels.h"
 
-__device__ __forceinline__ float softplus_naive(float x) { return logf(1.0f + expf(x)); }
-
 __global__ __launch_bounds__(256) void score_rows_kernel(const float* __restrict__ logits, int ld, int B, int NA, float temperature, int k,
                                                          float* __restrict__ max_score, int64_t* __restrict__ label, float* __restrict__ energy,
                                                          float* __restrict__ topk_val, int64_t* __restrict__ topk_idx, float* __restrict__ topk_energy) {

@@ -270,6 +270,41 @@ class Engine:
         self._seg_sumsq_valid = self._seg_sumsq is not None
         return self._io["loss"]
 
+    def energy_loss_backward(self, target_with_uq, m_in=25., m_out=0., weight=0.1, mce=False, grad_scale=1.0, accumulate=False):
+        """The train step of the reference's energy fine-tuning (tasks/gqa_energy.py:122-138, :144-145) on the last forward's logits: base loss
+        (BCE x NA, or with mce=True cross entropy x NA at the first maximum of the target row) + weight * the two energy-margin hinges, and backward
+        into the gradient arena.  target_with_uq [B, num_answers + 1] f32: the last column is the UQ flag (non-zero = unanswerable), read in place.
+        Returns (loss [1], energy [B] = E_f, label [B] int64 = sigmoid(logit).max(1)[1]) - engine-owned device tensors, overwritten by the next call;
+        `energy_loss_parts` holds (total, base loss, regulariser).  An empty subset gives a NaN loss and finite gradients, as the reference's
+        statements do."""
+        na = self.cfg.num_answers
+        t = target_with_uq
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.dim() != 2 or t.stride(1) != 1 or t.device != self.device:
+            raise ValueError("target_with_uq must be a 2-D f32 tensor with unit inner stride on %s" % self.device)
+        if self.shape is None or tuple(t.shape) != (self.shape[0], na + 1):
+            raise ValueError("target_with_uq must be [B, num_answers + 1] = [%s, %d] (the UQ column last); got %s" % (self.shape[0] if self.shape else "?", na + 1, tuple(t.shape)))
+        if not weight >= 0:
+            raise ValueError("weight must not be negative")
+        B = t.shape[0]
+        io = self._io
+        if "energy" not in io:
+            io["loss3"] = torch.zeros(3, dtype=torch.float32, device=self.device)
+            io["energy"] = torch.empty(B, dtype=torch.float32, device=self.device)
+            io["label"] = torch.empty(B, dtype=torch.int64, device=self.device)
+        if self._pending_clip is not None:
+            self.flush_deferred_clip() if accumulate else self.drop_deferred_clip()
+        check(self.lib.rgqa_engine_energy_loss_backward(self.h, ptr(t), t.stride(0), C.c_void_p(t.data_ptr() + 4 * na), t.stride(0), 1 if mce else 0, float(weight),
+                                                        float(m_in), float(m_out), float(grad_scale), ptr(io["loss3"]), ptr(io["energy"]), ptr(io["label"]),
+                                                        1 if accumulate else 0, _stream()))
+        self._wev_refs.pop("bwd", None)
+        self._seg_sumsq_valid = self._seg_sumsq is not None
+        return io["loss3"][:1], io["energy"], io["label"]
+
+    @property
+    def energy_loss_parts(self):
+        """[3] device tensor of the last energy_loss_backward: total, base loss, regulariser (None before the first call)"""
+        return self._io.get("loss3")
+
     def backward(self, dlogits, accumulate=False):
         dlogits = dlogits.contiguous().float()
         check(self.lib.rgqa_engine_backward(self.h, ptr(dlogits), dlogits.stride(0), 1 if accumulate else 0, _stream()))

@@ -21,7 +21,12 @@ and the Mahalanobis method (tasks/gqa_maha.py) for all three backbones, on the p
     loss = mean(-gaussian_score[b, pred_b]); loss.backward()                                                :240-244   maha_dpooled
     the whole batch step: forward, score, input step, second forward, score                                 :223-270   maha_scores
 
-with precision = W W^T factored once on the host (csrc/maha.hip).
+with precision = W W^T factored once on the host (csrc/maha.hip), and the loss head of the energy method's fine-tuning (tasks/gqa_energy.py:117-145,
+run/gqa_energy_finetune.bash) as one fused operator (`rgqa_op_energy_loss`, csrc/energy_loss.hip):
+
+    id_inds = target[:, -1] == 0; target = target[:, :-1]; BCE x NA (or --mceLoss: cross entropy x NA) and E_f                 :122-135   energy_loss_rows
+    loss += 0.1 * (relu(-E_f[id_inds] - m_in)**2).mean() + 0.1 * (relu(m_out + E_f[~id_inds])**2).mean()                      :137-138
+    the same under autograd, for `loss.backward()` through any drop-in model; label and score = E_f from the same pass        :122-145   energy_finetune_loss
 
 There is no CPU fallback: without the HIP library this raises."""
 import collections
@@ -37,6 +42,7 @@ OdinScores = collections.namedtuple("OdinScores", "score label logits feats_pt b
 MahaPack = collections.namedtuple("MahaPack", "mean precision W nu")
 MahaRows = collections.namedtuple("MahaRows", "score label y all_scores pooled")
 MahaScores = collections.namedtuple("MahaScores", "score label pooled feats_pt boxes_pt")
+EnergyLoss = collections.namedtuple("EnergyLoss", "loss base reg dlogits energy label")
 
 
 def score_rows(logits, temperature=1.0, k=0):
@@ -331,3 +337,61 @@ def maha_scores(model, feats, boxes, sent, pack, noise=0.0):
         x2 = _maha_forward(model, feats_pt, boxes_pt, sent)
     r2 = maha_score_rows(x2, pack)
     return MahaScores(r2.score, r2.label, x2, feats_pt, boxes_pt)
+
+
+# ------------------------------------------------------------------------------------------------ energy fine-tuning (tasks/gqa_energy.py:117-145)
+def _energy_loss_args(name, logits, target_with_uq, weight):
+    if not (isinstance(logits, torch.Tensor) and logits.is_cuda and logits.dtype == torch.float32 and logits.dim() == 2):
+        raise ValueError("%s: logits must be a 2-D float32 CUDA tensor" % name)
+    B, NA = logits.shape
+    t = target_with_uq
+    if not (isinstance(t, torch.Tensor) and t.dtype == torch.float32 and t.dim() == 2 and t.device == logits.device and tuple(t.shape) == (B, NA + 1)):
+        raise ValueError("%s: target_with_uq must be a float32 [B, NA + 1] = [%d, %d] tensor on the logits' device, the UQ column last" % (name, B, NA + 1))
+    if not weight >= 0:
+        raise ValueError("%s: weight must not be negative" % name)
+    return (logits if logits.stride(1) == 1 else logits.contiguous()), (t if t.stride(1) == 1 else t.contiguous())
+
+
+def energy_loss_rows(logits, target_with_uq, m_in=25.0, m_out=0.0, weight=0.1, mce_loss=False, grad_scale=1.0):
+    """gqa_energy.py:122-138 and :144-145 on given logits, one fused pass (`rgqa_op_energy_loss`).  logits: f32 CUDA [B, NA], any row stride;
+    target_with_uq: f32 [B, NA + 1], the last column the UQ flag (non-zero = unanswerable), read in place.  Returns EnergyLoss(loss, base, reg:
+    0-dim views of one [3] tensor; dlogits [B, NA] = d loss / d logits * grad_scale; energy [B] = E_f; label [B] int64 = sigmoid(logit).max(1)[1]).
+    An empty subset gives loss = reg = NaN and finite dlogits, as the reference's statements do."""
+    z, t = _energy_loss_args("energy_loss_rows", logits, target_with_uq, weight)
+    lib = _lib.load()
+    B, NA = z.shape
+    dev = z.device
+    n = C.c_size_t()
+    _lib.check(lib.rgqa_op_energy_loss_scratch_floats(B, C.byref(n)))
+    scratch = torch.empty(n.value, dtype=torch.float32, device=dev)
+    loss = torch.empty(3, dtype=torch.float32, device=dev)
+    dl = torch.empty(B, NA, dtype=torch.float32, device=dev)
+    en = torch.empty(B, dtype=torch.float32, device=dev)
+    lab = torch.empty(B, dtype=torch.int64, device=dev)
+    p = _lib.ptr
+    _lib.check(lib.rgqa_op_energy_loss(p(z), z.stride(0), p(t), t.stride(0), C.c_void_p(t.data_ptr() + 4 * NA), t.stride(0), B, NA, NA, 1 if mce_loss else 0,
+                                       float(weight), float(m_in), float(m_out), float(grad_scale), p(loss), p(dl), dl.stride(0), p(en), p(lab), p(scratch), _stream(dev)))
+    return EnergyLoss(loss[0], loss[1], loss[2], dl, en, lab)
+
+
+class _EnergyFinetuneLoss(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, logit, target_with_uq, m_in, m_out, weight, mce_loss):
+        r = energy_loss_rows(logit.detach(), target_with_uq, m_in, m_out, weight, mce_loss)
+        ctx.save_for_backward(r.dlogits)
+        ctx.mark_non_differentiable(r.energy, r.label)
+        return r.loss.clone(), r.energy, r.label
+
+    @staticmethod
+    def backward(ctx, grad_loss, *unused):
+        dl, = ctx.saved_tensors
+        return grad_loss * dl, None, None, None, None, None
+
+
+def energy_finetune_loss(logit, target_with_uq, m_in, m_out, weight=0.1, mce_loss=False):
+    """What a trainer puts in place of gqa_energy.py:122-138 and :144-145: `loss, score, label = energy_finetune_loss(model(feats, boxes, sent), target,
+    args.m_in, args.m_out, mce_loss=args.mceLoss)` with `target` as the loader gives it (UQ column last); `loss.backward()`, `clip_grad_norm_` and
+    `BertAdam.step()` stay as they are.  logit: the [B, NA] f32 CUDA output of GQAModel / GQAUNITER / GQABUTD.  Returns (loss 0-dim, E_f [B], label
+    [B]): the forward runs the fused operator once and keeps dlogits, the backward hands `grad_output * dlogits` to the model's autograd boundary."""
+    _energy_loss_args("energy_finetune_loss", logit, target_with_uq, weight)
+    return _EnergyFinetuneLoss.apply(logit, target_with_uq, float(m_in), float(m_out), float(weight), bool(mce_loss))

@@ -1,0 +1,141 @@
+// driver of the host build of csrc/energy_loss.hip (kernels.h beside it): small shapes against straightforward f64 loops of tasks/gqa_energy.py:122-138.
+// Every operand sits in an allocation of exactly its size (a sanitizer build sees any access past it), outputs carry guard columns, and each case runs
+// twice - operands 16-byte aligned with pitches that allow 16-byte accesses, and shifted by one float with odd pitches - and must give the same bits.
+#include "rgqa_amd/csrc/energy_loss.cpp"
+#include <random>
+static std::mt19937 rng(1);
+static float rnd() { return std::normal_distribution<float>(0, 1)(rng); }
+struct Out { std::vector<float> loss, dl, en; std::vector<int64_t> lab; };
+// layout 0: aligned, pitches multiples of 4; layout 1: every base one float off, odd pitches
+static int run(int layout, int B, int NA, int NAp, const std::vector<float>& z, const std::vector<float>& t, const EnergyLossCfg& c, float gs, Out& o, bool want_loss = true) {
+    const int off = layout, ld = layout ? NA + 3 + (NA % 2 == 0) : (NA + 3) / 4 * 4 + 4, ldt = NA + 1, ldd = layout ? NAp + 1 + (NAp % 2 == 0) : (NAp + 3) / 4 * 4;
+    // rows of the last operand row end exactly at the end of the allocation: ld * (B - 1) + NA floats
+    std::vector<float> zb(off + (size_t)ld * (B - 1) + NA), tb(off + (size_t)ldt * (B - 1) + NA + 1), db(off + (size_t)ldd * (B - 1) + ldd, 7.f);
+    for (int b = 0; b < B; ++b) { memcpy(&zb[off + (size_t)b * ld], &z[(size_t)b * NA], 4 * NA); memcpy(&tb[off + (size_t)b * ldt], &t[(size_t)b * (NA + 1)], 4 * (NA + 1)); }
+    size_t ns = k_energy_loss_scratch_floats(B);
+    std::vector<float> scratch(ns + 8, 5.f);
+    o.loss.assign(3 + 2, 9.f); o.en.assign(B + 2, 9.f); o.lab.assign(B + 2, -5);
+    int rc = k_energy_loss(zb.data() + off, ld, tb.data() + off, ldt, tb.data() + off + NA, ldt, B, NA, NAp, c, gs, want_loss ? o.loss.data() : nullptr, db.data() + off, ldd, o.en.data(), o.lab.data(),
+                           want_loss ? scratch.data() : nullptr, nullptr);
+    if (rc) return 1000;
+    int bad = 0;
+    for (size_t i = ns; i < ns + 8; ++i) if (scratch[i] != 5.f) ++bad;
+    if (o.loss[3] != 9.f || o.loss[4] != 9.f || o.en[B] != 9.f || o.lab[B] != -5) ++bad;
+    for (int i = 0; i < off; ++i) if (db[i] != 7.f) ++bad;
+    o.dl.assign((size_t)B * NAp, 0.f);
+    for (int b = 0; b < B; ++b) {
+        for (int n = 0; n < NAp; ++n) o.dl[(size_t)b * NAp + n] = db[off + (size_t)b * ldd + n];
+        for (int n = NAp; n < ldd; ++n) if (db[off + (size_t)b * ldd + n] != 7.f) ++bad;
+    }
+    if (bad) printf("guard words overwritten (%d)\n", bad);
+    return bad;
+}
+static int check(int B, int NA, int NAp, int mce, int ood_mode /* 0 mixed, 1 none, 2 all */, float weight, bool once = false /* the shifted layout alone (a case of many rows) */) {
+    std::vector<float> z((size_t)B * NA), t((size_t)B * (NA + 1), 0.f);
+    for (auto& v : z) v = 3.f * rnd() - 6.f;
+    for (int b = 0; b < B; ++b) {
+        const bool ood = ood_mode == 2 || (ood_mode == 0 && b % 3 == 1);
+        if (ood) t[(size_t)b * (NA + 1) + NA] = 1.f;
+        else { t[(size_t)b * (NA + 1) + (b * 7) % NA] = 0.9f; t[(size_t)b * (NA + 1) + (b * 7 + 3) % NA] = 0.3f; }
+    }
+    if (B > 2) { z[2 * (size_t)NA + NA - 1] = 5.f; z[2 * (size_t)NA + 1] = 5.f; }      // a tie of the row maximum: the first index wins
+    // f64 reference
+    std::vector<double> E(B), share(B), h(B), cb(B);
+    std::vector<int> lab(B), tgt(B);
+    int n_out = 0;
+    for (int b = 0; b < B; ++b) n_out += t[(size_t)b * (NA + 1) + NA] != 0.f;
+    const int n_in = B - n_out;
+    double m_in = 0, m_out = 0;
+    for (int pass = 0; pass < 2; ++pass) {
+        std::vector<double> ein, eout;
+        for (int b = 0; b < B; ++b) {
+            const float* x = &z[(size_t)b * NA]; const float* y = &t[(size_t)b * (NA + 1)];
+            double s = 0, e = 0, zm = -1e300, best = -1; int bi = 0, ti = 0; double tv = -1e300;
+            for (int n = 0; n < NA; ++n) {
+                s += std::max((double)x[n], 0.0) - (double)x[n] * y[n] + log1p(exp(-fabs((double)x[n])));
+                e += log(1 + exp((double)x[n]));
+                zm = std::max(zm, (double)x[n]);
+                const float sg = 1.0f / (1.0f + expf(-x[n]));
+                if (sg > best) { best = sg; bi = n; }
+                if (y[n] > tv) { tv = y[n]; ti = n; }
+            }
+            if (mce) { double se = 0; for (int n = 0; n < NA; ++n) se += exp(x[n] - zm); e = zm + log(se); s = e - x[ti]; }
+            E[b] = e; share[b] = s; lab[b] = bi; tgt[b] = ti;
+            const bool ood = y[NA] != 0.f;
+            (ood ? eout : ein).push_back(e);
+            h[b] = ood ? std::max(m_out + e, 0.0) : std::max(-e - m_in, 0.0);
+            cb[b] = ood ? 2.0 * weight * h[b] / n_out : -2.0 * weight * h[b] / n_in;
+        }
+        if (pass == 0) {      // margins at the medians: active and inactive hinges in both subsets
+            std::sort(ein.begin(), ein.end()); std::sort(eout.begin(), eout.end());
+            m_in = ein.empty() ? 25.0 : (double)(float)-ein[(ein.size() - 1) / 2];
+            m_out = eout.empty() ? 0.0 : (double)(float)-eout[(eout.size() - 1) / 2];
+        }
+    }
+    double base = 0, hin = 0, hout = 0;
+    for (int b = 0; b < B; ++b) { base += share[b]; (t[(size_t)b * (NA + 1) + NA] != 0.f ? hout : hin) += h[b] * h[b]; }
+    base = (mce ? NA * base : base) / B;
+    const double reg = weight * (hin / n_in) + weight * (hout / n_out);
+    const EnergyLossCfg c = {mce, weight, (float)m_in, (float)m_out};
+    Out o0, o1, o2;
+    int bad = 0;
+    if (once) { bad = run(1, B, NA, NAp, z, t, c, 1.0f, o0); o1 = o0; o2 = o0; for (auto& v : o2.dl) v *= 0.5f; o2.loss[0] = 9.f; }
+    else bad = run(0, B, NA, NAp, z, t, c, 1.0f, o0) + run(1, B, NA, NAp, z, t, c, 1.0f, o1) + run(1, B, NA, NAp, z, t, c, 0.5f, o2, false);
+    if (memcmp(o0.loss.data(), o1.loss.data(), 12) || memcmp(o0.dl.data(), o1.dl.data(), 4 * o0.dl.size()) || memcmp(o0.en.data(), o1.en.data(), 4 * B) || o0.lab != o1.lab) {
+        printf("the two layouts differ\n"); ++bad;
+    }
+    auto close = [](double g, double r, double tol, double floor = 1e-30) { return (std::isnan(r) && std::isnan(g)) || std::fabs(g - r) <= tol * std::fabs(r) + floor; };
+    // (the row AT the median sits on its hinge's edge once the margin is rounded to f32: its square, 1e-15 or so, is there or not)
+    if (!close(o0.loss[0], base + reg, 1e-6) || !close(o0.loss[1], base, 1e-6) || !close(o0.loss[2], reg, 1e-5, 1e-9 * std::fabs(base))) {
+        printf("loss got %.9g %.9g %.9g ref %.9g %.9g %.9g\n", o0.loss[0], o0.loss[1], o0.loss[2], base + reg, base, reg); ++bad;
+    }
+    if (o2.loss[0] != 9.f) { printf("loss written though not asked for\n"); ++bad; }
+    double dmax = 0;
+    std::vector<double> dref((size_t)B * NAp, 0.0);
+    for (int b = 0; b < B; ++b) {
+        const float* x = &z[(size_t)b * NA]; const float* y = &t[(size_t)b * (NA + 1)];
+        if (!close(o0.en[b], E[b], 2e-6)) { if (bad < 5) printf("energy b=%d got %.9g ref %.9g\n", b, o0.en[b], E[b]); ++bad; }
+        if (o0.lab[b] != lab[b]) { printf("label b=%d got %ld ref %d\n", b, (long)o0.lab[b], lab[b]); ++bad; }
+        for (int n = 0; n < NA; ++n) {
+            const double p = mce ? exp(x[n] - E[b]) : 1.0 / (1.0 + exp(-(double)x[n]));
+            dref[(size_t)b * NAp + n] = mce ? ((double)NA / B) * (p - (n == tgt[b])) + cb[b] * p : (p - y[n]) / B + cb[b] * p;
+            dmax = std::max(dmax, std::fabs(dref[(size_t)b * NAp + n]));
+        }
+    }
+    int active_in = 0, active_out = 0;
+    for (int b = 0; b < B; ++b) (t[(size_t)b * (NA + 1) + NA] != 0.f ? active_out : active_in) += h[b] > 0;
+    for (size_t i = 0; i < dref.size(); ++i) {
+        if (std::fabs(o0.dl[i] - dref[i]) > 2e-5 * dmax) { if (bad < 5) printf("dlogits[%zu] got %.9g ref %.9g (max %.3g)\n", i, o0.dl[i], dref[i], dmax); ++bad; }
+        if ((int)(i % NAp) >= NA && (o0.dl[i] != 0.f || std::signbit(o0.dl[i]))) { printf("padding not +0\n"); ++bad; }
+        if (o2.dl[i] != 0.5f * o0.dl[i]) { if (bad < 5) printf("grad_scale 0.5 does not halve dlogits[%zu]\n", i); ++bad; }
+    }
+    printf("energy_loss B=%d NA=%d NAp=%d mce=%d ood_mode=%d weight=%g: active hinges %d of %d ID, %d of %d OOD; %d bad\n", B, NA, NAp, mce, ood_mode, weight, active_in, n_in,
+           active_out, n_out, bad);
+    if (weight > 0 && ((n_in >= 3 && active_in == 0) || (n_out >= 2 && active_out == 0))) { printf("no active hinge: the case checks nothing\n"); ++bad; }
+    return bad;
+}
+int main(int argc, char** argv) {
+    // a workgroup costs 256 host threads: the default set keeps to ~70 of them (seconds); "full" adds the larger shapes (a minute)
+    const bool full = argc > 1 && !strcmp(argv[1], "full");
+    int bad = 0;
+    for (int mce = 0; mce < 2; ++mce) {
+        bad += check(5, 67, 128, mce, 0, 0.1f);
+        bad += check(3, 1842, 1856, mce, 0, 0.1f, true);       // more than one quad sweep per thread (1842 > 4 * 256)
+        bad += check(4, 67, 128, mce, 1, 0.1f, true);          // no OOD row: NaN loss, finite gradient
+        bad += check(4, 67, 128, mce, 2, 0.1f, true);          // no ID row
+        if (!full) continue;
+        bad += check(7, 300, 320, mce, 0, 0.1f);
+        bad += check(9, 1030, 1030, mce, 0, 0.25f);            // NAp = NA, not a multiple of 4
+        if (!mce) bad += check(300, 67, 67, mce, 0, 0.1f, true);      // more rows than the 256 threads of the fold
+        bad += check(5, 67, 128, mce, 0, 0.0f);
+    }
+    EnergyLossCfg c = {0, -1.f, 0.f, 0.f};
+    float x[8] = {0};
+    if (k_energy_loss(x, 4, x, 4, x, 1, 1, 4, 4, c, 1.f, nullptr, nullptr, 0, nullptr, nullptr, nullptr, nullptr) == 0) { printf("negative weight accepted\n"); ++bad; }
+    c.weight = 0.1f;
+    if (k_energy_loss(x, 4, x, 4, x, 1, 1, 4, 4, c, 1.f, x, nullptr, 0, nullptr, nullptr, nullptr, nullptr) == 0) { printf("loss without scratch accepted\n"); ++bad; }
+    if (k_energy_loss(x, 3, x, 4, x, 1, 1, 4, 4, c, 1.f, nullptr, nullptr, 0, nullptr, nullptr, nullptr, nullptr) == 0) { printf("ld < NA accepted\n"); ++bad; }
+    if (k_energy_loss(x, 4, x, 4, x, 1, 1, 4, 8, c, 1.f, nullptr, x, 4, nullptr, nullptr, nullptr, nullptr) == 0) { printf("ldd < NAp accepted\n"); ++bad; }
+    printf("TOTAL bad %d\n", bad);
+    return bad != 0;
+}
