@@ -142,6 +142,14 @@ int rgqa_engine_loss_backward(rgqa_engine* e, const float* target, int ld_target
 int rgqa_engine_energy_loss_backward(rgqa_engine* e, const float* target, int ld_target, const float* ood_flag, int ld_flag, int mce, float weight,
                                      float m_in, float m_out, float grad_scale, float* loss3, float* energy, int64_t* label, int accumulate,
                                      void* stream);
+/* The train step of the soft resampling (tasks/gqa_resampling.py:176-220) on ONE forward of the concatenated [positive ; negative] batch:
+ * rgqa_op_resample_loss (below) on the last forward's logits + full backward into the grad arena, every precision, every backbone.  target [B, ld_target >=
+ * num_answers] f32 (a target that carries the UQ column is passed as is: the column is not read); rows [0, n_pos) are positive, 1 <= n_pos < B; weights
+ * [B - n_pos] f32 on the device, from rgqa_resample_weights.  loss3 (3 floats: loss, loss_pos, loss_neg) and row_loss [B - n_pos]: device buffers, each may be
+ * NULL.  The f32 dlogits are written where rgqa_engine_loss_backward writes them and take the same path from there: after any call the gradient arena has
+ * the bits of rgqa_engine_backward on the operator's dlogits.  Honours rgqa_engine_set_input_grads. */
+int rgqa_engine_resample_loss_backward(rgqa_engine* e, const float* target, int ld_target, int n_pos, const float* weights, float grad_scale, float* loss3,
+                                       float* row_loss, int accumulate, void* stream);
 /* backward from a caller-supplied dL/dlogits [B,num_answers] f32 (autograd integration) */
 int rgqa_engine_backward(rgqa_engine* e, const float* dlogits, int ld, int accumulate, void* stream);
 /* backward from dL/dpooled [B,hidden] f32 with row stride ld >= hidden (any alignment): LXRTEncoder used under a caller-owned head
@@ -423,6 +431,26 @@ int rgqa_op_energy_loss_scratch_floats(int B, size_t* out);
 int rgqa_op_energy_loss(const float* logits, int ld, const float* target, int ld_target, const float* ood_flag, int ld_flag, int B, int NA, int NAp,
                         int mce, float weight, float m_in, float m_out, float grad_scale, float* loss3, float* dlogits, int ldd, float* energy,
                         int64_t* label, float* scratch, void* stream);
+/* Soft resampling of the hard unanswerable questions (tasks/gqa_resampling.py:176-220, the lxmert / uniter order of :213-220; rgqa_amd/csrc/resample.hip).
+ * theta [N] f32: one learnable weight parameter per negative training question; wid [Bn] int64: the parameter of each negative row (duplicates are normal;
+ * an index outside [0, N) is skipped, its weight is 0).  With w = softplus(theta) (torch's: theta above 20), m1 = mean w, mh = mean sqrt w:
+ *   rgqa_resample_weights:  stats = {m1, mh} (two doubles, sums over N in f64), weights[b] = (float)(mh / m1) sqrtf(w[wid[b]])                   :184-186
+ *   rgqa_op_resample_loss:  rows [0, n_pos) positive, rows [n_pos, B) negative; r_b = sum_c BCEWithLogits(z[b, c], t[b, c]);
+ *                           loss3 = {loss_pos + loss_neg, loss_pos = mean r_b, loss_neg = mean weights_b r_b}; row_loss [B - n_pos] = r_b;        :196-202
+ *                           dlogits [B, ldd >= NAp >= NA] f32 = (sigmoid(z) - t) c_b grad_scale, c_b = 1 / n_pos | weights_b / (B - n_pos), columns NA .. NAp
+ *                           exact zeros.  loss3, dlogits, row_loss may each be NULL; loss3 needs `scratch`.
+ *   rgqa_resample_step:     g = d(-loss_neg) / d theta in closed form (dense: every entry moves through m1 and mh), written to grad_out [N] if not NULL;
+ *                           momentum_buf <- momentum momentum_buf + g; theta <- theta - lr momentum_buf (torch.optim.SGD; a zero buffer gives its
+ *                           first step).  stats must be rgqa_resample_weights' of the same theta, wid / row_loss those of the batch.             :203, :218-220
+ * `scratch`: rgqa_resample_scratch_floats(N, B) floats (any content; B >= the number of rows of any of the calls) - the query needs no device.  No float
+ * atomics: every output repeats bit for bit and does not depend on the operands' alignment; positive rows, and negative rows of weight 1, have the dlogits
+ * bits of rgqa_op_bce on those rows alone. */
+int rgqa_resample_scratch_floats(int N, int B, size_t* out);
+int rgqa_resample_weights(const float* theta, int N, const int64_t* wid, int Bn, double* stats, float* weights, float* scratch, void* stream);
+int rgqa_op_resample_loss(const float* logits, int ld, const float* target, int ld_target, int B, int n_pos, int NA, int NAp, const float* weights,
+                          float grad_scale, float* loss3, float* dlogits, int ldd, float* row_loss, float* scratch, void* stream);
+int rgqa_resample_step(float* theta, float* momentum_buf, int N, const int64_t* wid, const float* row_loss, int Bn, const double* stats, float lr,
+                       float momentum, float* grad_out, float* scratch, void* stream);
 
 #ifdef __cplusplus
 }

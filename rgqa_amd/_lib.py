@@ -37,6 +37,7 @@ SIGNATURES = {
     "rgqa_engine_forward": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _u64, _vp],
     "rgqa_engine_loss_backward": [_vp, _vp, _i, _vp, _f, _i, _vp],
     "rgqa_engine_energy_loss_backward": [_vp, _vp, _i, _vp, _i, _i, _f, _f, _f, _f, _vp, _vp, _vp, _i, _vp],
+    "rgqa_engine_resample_loss_backward": [_vp, _vp, _i, _i, _vp, _f, _vp, _vp, _i, _vp],
     "rgqa_engine_backward": [_vp, _vp, _i, _i, _vp],
     "rgqa_engine_backward_pooled": [_vp, _vp, _i, _i, _vp],
     "rgqa_engine_get_activation": [_vp, C.c_char_p, _vp, _sz, _vp],
@@ -90,6 +91,10 @@ SIGNATURES = {
     "rgqa_op_bce": [_vp, _vp, _vp, _vp, _i, _i, _vp],
     "rgqa_op_energy_loss_scratch_floats": [_i, C.POINTER(_sz)],
     "rgqa_op_energy_loss": [_vp, _i, _vp, _i, _vp, _i, _i, _i, _i, _i, _f, _f, _f, _f, _vp, _vp, _i, _vp, _vp, _vp, _vp],
+    "rgqa_resample_scratch_floats": [_i, _i, C.POINTER(_sz)],
+    "rgqa_resample_weights": [_vp, _i, _vp, _i, _vp, _vp, _vp, _vp],
+    "rgqa_op_resample_loss": [_vp, _i, _vp, _i, _i, _i, _i, _i, _vp, _f, _vp, _vp, _i, _vp, _vp, _vp],
+    "rgqa_resample_step": [_vp, _vp, _i, _vp, _vp, _i, _vp, _f, _f, _vp, _vp, _vp],
     "rgqa_batch_prepare": [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp],
     "rgqa_host_gather_rows": [_vp, _sz, _sz, _vp, _i, _vp, _i],
     "rgqa_score_rows": [_vp, _i, _i, _i, C.c_float, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp],

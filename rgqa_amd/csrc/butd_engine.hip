@@ -365,6 +365,15 @@ public:
         CKB(k_cast_pad<TB>(dl32, NAp, dlogits, NAp, B, NAp, 1.0f, s));
         return backward_impl(accumulate, s);
     }
+    int resample_loss_backward(const float* target, int ldt, int n_pos, const float* weights, float grad_scale, float* loss3, float* row_loss, int accumulate,
+                               hipStream_t s) override {
+        RGQA_REQUIRE(have_fwd && G != nullptr, "resample_loss_backward: no forward pass recorded / no gradient arena");
+        float* dl32 = dwscr;
+        RGQA_REQUIRE(k_resample_scratch_floats(0, B) <= partial_floats, "resample_loss_backward: batch %d exceeds the scratch", B);
+        CKB(k_resample_loss(logits, NAp, target, ldt, B, n_pos, NA, NAp, weights, grad_scale, loss3, dl32, NAp, row_loss, partial, s));      // (partial: as energy_loss_backward)
+        CKB(k_cast_pad<TB>(dl32, NAp, dlogits, NAp, B, NAp, 1.0f, s));
+        return backward_impl(accumulate, s);
+    }
     int backward(const float* dl, int ldd, int accumulate, hipStream_t s) override {
         RGQA_REQUIRE(have_fwd && G != nullptr && dl != nullptr, "backward: no forward pass recorded / null argument");
         CKB(k_cast_pad<TB>(dl, ldd, dlogits, NAp, B, NA, 1.0f, s));

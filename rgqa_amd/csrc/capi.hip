@@ -148,6 +148,12 @@ int rgqa_engine_energy_loss_backward(rgqa_engine* e, const float* target, int ld
     const EnergyLossCfg c = {mce ? 1 : 0, weight, m_in, m_out};
     return e->impl->energy_loss_backward(target, ldt, ood_flag, ld_flag, c, grad_scale, loss3, energy, label, accumulate, S(stream));
 }
+int rgqa_engine_resample_loss_backward(rgqa_engine* e, const float* target, int ldt, int n_pos, const float* weights, float grad_scale, float* loss3, float* row_loss,
+                                       int accumulate, void* stream) {
+    NEED(e);
+    RGQA_REQUIRE(target != nullptr && weights != nullptr, "resample_loss_backward: null target / weights pointer");
+    return e->impl->resample_loss_backward(target, ldt, n_pos, weights, grad_scale, loss3, row_loss, accumulate, S(stream));
+}
 int rgqa_engine_backward(rgqa_engine* e, const float* dlogits, int ld, int accumulate, void* stream) {
     NEED(e);
     return e->impl->backward(dlogits, ld, accumulate, S(stream));
@@ -464,6 +470,22 @@ int rgqa_op_energy_loss(const float* logits, int ld, const float* target, int ld
                         float m_in, float m_out, float grad_scale, float* loss3, float* dlogits, int ldd, float* energy, int64_t* label, float* scratch, void* stream) {
     const EnergyLossCfg c = {mce ? 1 : 0, weight, m_in, m_out};
     return k_energy_loss(logits, ld, target, ld_target, ood_flag, ld_flag, B, NA, NAp, c, grad_scale, loss3, dlogits, ldd, energy, label, scratch, S(stream));
+}
+int rgqa_resample_scratch_floats(int N, int B, size_t* out) {
+    RGQA_REQUIRE(N > 0 && B > 0 && out != nullptr, "resample_scratch_floats: bad argument");
+    *out = k_resample_scratch_floats(N, B);
+    return RGQA_OK;
+}
+int rgqa_resample_weights(const float* theta, int N, const int64_t* wid, int Bn, double* stats, float* weights, float* scratch, void* stream) {
+    return k_resample_weights(theta, N, wid, Bn, stats, weights, scratch, S(stream));
+}
+int rgqa_op_resample_loss(const float* logits, int ld, const float* target, int ld_target, int B, int n_pos, int NA, int NAp, const float* weights, float grad_scale,
+                          float* loss3, float* dlogits, int ldd, float* row_loss, float* scratch, void* stream) {
+    return k_resample_loss(logits, ld, target, ld_target, B, n_pos, NA, NAp, weights, grad_scale, loss3, dlogits, ldd, row_loss, scratch, S(stream));
+}
+int rgqa_resample_step(float* theta, float* momentum_buf, int N, const int64_t* wid, const float* row_loss, int Bn, const double* stats, float lr, float momentum,
+                       float* grad_out, float* scratch, void* stream) {
+    return k_resample_step(theta, momentum_buf, N, wid, row_loss, Bn, stats, lr, momentum, grad_out, scratch, S(stream));
 }
 int rgqa_op_bce(const float* logits, const float* target, float* loss, float* dlogits, int B, int NA, void* stream) {
     return k_bce_fwd_bwd(logits, NA, target, NA, loss, dlogits, NA, B, NA, NA, 1.0f, S(stream));

@@ -111,6 +111,10 @@ public:
     // writes them and take the same path from there.  loss3 {total, base, regulariser}, energy [B], label [B]: caller's device buffers, each may be null
     virtual int energy_loss_backward(const float* target, int ldt, const float* ood_flag, int ldf, const EnergyLossCfg& c, float grad_scale, float* loss3, float* energy,
                                      int64_t* label, int accumulate, hipStream_t s) = 0;
+    // the row-weighted BCE head of the soft resampling (tasks/gqa_resampling.py:196-202; resample.hip) + backward: rows [0, n_pos) positive, the rest weighted by
+    // weights [B - n_pos] (device).  loss3 {loss, loss_pos, loss_neg}, row_loss [B - n_pos]: caller's device buffers, each may be null
+    virtual int resample_loss_backward(const float* target, int ldt, int n_pos, const float* weights, float grad_scale, float* loss3, float* row_loss, int accumulate,
+                                       hipStream_t s) = 0;
     virtual int backward(const float* dlogits, int ldd, int accumulate, hipStream_t s) = 0;
     virtual int backward_pooled(const float* dpooled, int ld, int accumulate, hipStream_t s) = 0;
     // gradient-arena ranges in the order backward finishes them (for overlapping the DP exchange with backward)

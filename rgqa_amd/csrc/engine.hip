@@ -1157,6 +1157,17 @@ public:
         CKP(PC_OTHER, k_cast_pad<TB>(dl32, NAp, dlogits, NAp, B, NAp, 1.0f, s));
         return backward_impl(accumulate, s);
     }
+    int resample_loss_backward(const float* target, int ldt, int n_pos, const float* weights, float grad_scale, float* loss3, float* row_loss, int accumulate,
+                               hipStream_t s) override {
+        RGQA_REQUIRE(have_fwd, "resample_loss_backward: no forward pass recorded");
+        RGQA_REQUIRE(G != nullptr, "resample_loss_backward: no gradient arena bound");
+        prof_block = PB_HEAD;
+        float* dl32 = part;   // as loss_backward: [B, NAp] f32, the row shares of the loss behind it
+        RGQA_REQUIRE((size_t)B * NAp + k_resample_scratch_floats(0, B) <= part_floats, "resample_loss_backward: batch %d exceeds the scratch", B);
+        CKP(PC_OTHER, k_resample_loss(logits, NAp, target, ldt, B, n_pos, cfg.num_answers, NAp, weights, grad_scale, loss3, dl32, NAp, row_loss, part + (size_t)B * NAp, s));
+        CKP(PC_OTHER, k_cast_pad<TB>(dl32, NAp, dlogits, NAp, B, NAp, 1.0f, s));
+        return backward_impl(accumulate, s);
+    }
     int backward(const float* dl, int ldd, int accumulate, hipStream_t s) override {
         RGQA_REQUIRE(have_fwd, "backward: no forward pass recorded");
         RGQA_REQUIRE(G != nullptr && dl != nullptr, "backward: null gradient arena / dlogits");

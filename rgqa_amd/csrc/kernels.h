@@ -198,6 +198,19 @@ size_t k_energy_loss_scratch_floats(int B);
 int k_energy_loss(const float* logits, int ld, const float* target, int ldt, const float* ood_flag, int ldf, int B, int NA, int NAp, const EnergyLossCfg& c, float grad_scale,
                   float* loss3, float* dlogits, int ldd, float* energy, int64_t* label, float* scratch, hipStream_t s);
 
+// ---- resample.hip: the step of the soft resampling of the unanswerable questions (tasks/gqa_resampling.py:176-220): batch weights from the N weight
+// parameters, the row-weighted BCE head, and the closed-form gradient of the weight parameters with its SGD-momentum update
+size_t k_resample_scratch_floats(int N, int B);      // what any of the three calls below needs (N = 0: the loss call alone)
+// stats[0..1] = mean softplus(theta), mean sqrt softplus(theta) (f64);  weights[b] = (float)(mh / m1) sqrtf(softplus(theta[wid[b]])), 0 for an index outside [0, N)
+int k_resample_weights(const float* theta, int N, const int64_t* wid, int Bn, double* stats, float* weights, float* scratch, hipStream_t s);
+// rows [0, n_pos) positive (c_b = 1 / n_pos), the rest negative (c_b = weights[b - n_pos] / (B - n_pos)).  Outputs, each may be null: loss3 = {loss, loss_pos,
+// loss_neg} (needs `scratch`), dlogits [B, NAp] f32 = (sigmoid(z) - t) c_b grad_scale (columns NA .. NAp exact zeros), row_loss [B - n_pos] = the negative rows' BCE sums
+int k_resample_loss(const float* logits, int ld, const float* target, int ldt, int B, int n_pos, int NA, int NAp, const float* weights, float grad_scale, float* loss3,
+                    float* dlogits, int ldd, float* row_loss, float* scratch, hipStream_t s);
+// g = d(-loss_neg) / d theta in closed form (written to grad_out [N] if not null); buf <- momentum buf + g; theta <- theta - lr buf.  stats: k_resample_weights' of the same theta
+int k_resample_step(float* theta, float* buf, int N, const int64_t* wid, const float* row_loss, int Bn, const double* stats, float lr, float momentum, float* grad_out,
+                    float* scratch, hipStream_t s);
+
 // ---- optim.hip
 int k_sumsq(const float* g, size_t n, float* partial /* >= 1025 floats, any content ([1024] = ticket word, zeroed on the stream by the call) */, float* out_sumsq, int accumulate_into_out, hipStream_t s);
 // several owned ranges in one launch (each with partials / ticket / output slot of its own, as k_sumsq_owned; never accumulating)

@@ -305,6 +305,43 @@ class Engine:
         """[3] device tensor of the last energy_loss_backward: total, base loss, regulariser (None before the first call)"""
         return self._io.get("loss3")
 
+    def resample_loss_backward(self, target, n_pos, weights, grad_scale=1.0, accumulate=False):
+        """The train step of the reference's soft resampling (tasks/gqa_resampling.py:196-202) on the last forward's logits - ONE forward of the
+        concatenated [positive ; negative] batch: rows [0, n_pos) take 1 / n_pos, row n_pos + b takes weights[b] / (B - n_pos), BCE summed over the
+        answers, and backward into the gradient arena.  target [B, num_answers] or [B, num_answers + 1] f32 (the UQ column is not read); weights
+        [B - n_pos] f32 on the device (ResampleWeights.batch_weights).  Returns (loss [1], row_loss [B - n_pos] = the negative rows' BCE sums, what
+        ResampleWeights.step takes) - engine-owned device tensors, overwritten by the next call; `resample_loss_parts` holds (loss, loss_pos,
+        loss_neg)."""
+        na = self.cfg.num_answers
+        t = target
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.dim() != 2 or t.stride(1) != 1 or t.device != self.device:
+            raise ValueError("target must be a 2-D f32 tensor with unit inner stride on %s" % self.device)
+        if self.shape is None or t.shape[0] != self.shape[0] or t.shape[1] not in (na, na + 1):
+            raise ValueError("target must be [B, num_answers (+ 1)] = [%s, %d (+ 1)]; got %s" % (self.shape[0] if self.shape else "?", na, tuple(t.shape)))
+        B = t.shape[0]
+        n_pos = int(n_pos)
+        if not 1 <= n_pos < B:
+            raise ValueError("n_pos must be in [1, B) = [1, %d); got %d" % (B, n_pos))
+        w = weights
+        if not isinstance(w, torch.Tensor) or w.dtype != torch.float32 or w.device != self.device or tuple(w.shape) != (B - n_pos,) or not w.is_contiguous():
+            raise ValueError("weights must be a contiguous f32 [B - n_pos] = [%d] tensor on %s" % (B - n_pos, self.device))
+        io = self._io
+        if "rs_row_loss" not in io or io["rs_row_loss"].numel() != B - n_pos:
+            io.setdefault("rs_loss3", torch.zeros(3, dtype=torch.float32, device=self.device))
+            io["rs_row_loss"] = torch.empty(B - n_pos, dtype=torch.float32, device=self.device)
+        if self._pending_clip is not None:
+            self.flush_deferred_clip() if accumulate else self.drop_deferred_clip()
+        check(self.lib.rgqa_engine_resample_loss_backward(self.h, ptr(t), t.stride(0), n_pos, ptr(w), float(grad_scale), ptr(io["rs_loss3"]), ptr(io["rs_row_loss"]),
+                                                          1 if accumulate else 0, _stream()))
+        self._wev_refs.pop("bwd", None)
+        self._seg_sumsq_valid = self._seg_sumsq is not None
+        return io["rs_loss3"][:1], io["rs_row_loss"]
+
+    @property
+    def resample_loss_parts(self):
+        """[3] device tensor of the last resample_loss_backward: loss, loss_pos, loss_neg (None before the first call)"""
+        return self._io.get("rs_loss3")
+
     def backward(self, dlogits, accumulate=False):
         dlogits = dlogits.contiguous().float()
         check(self.lib.rgqa_engine_backward(self.h, ptr(dlogits), dlogits.stride(0), 1 if accumulate else 0, _stream()))

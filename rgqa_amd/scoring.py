@@ -28,6 +28,12 @@ run/gqa_energy_finetune.bash) as one fused operator (`rgqa_op_energy_loss`, csrc
     loss += 0.1 * (relu(-E_f[id_inds] - m_in)**2).mean() + 0.1 * (relu(m_out + E_f[~id_inds])**2).mean()                      :137-138
     the same under autograd, for `loss.backward()` through any drop-in model; label and score = E_f from the same pass        :122-145   energy_finetune_loss
 
+and the loss head of the soft resampling of the unanswerable questions (tasks/gqa_resampling.py:176-220, lxmert / uniter order; csrc/resample.hip) on ONE
+forward of the concatenated [positive ; negative] batch (the weight parameters themselves: rgqa_amd/resample.py):
+
+    loss_pos = mean(bce(logit_pos, target_pos)) * NA;  loss_neg = (weights @ bce(logit_neg, target_neg)).sum() / Bn           :196-200   resample_loss_rows
+    loss = loss_pos + loss_neg;  loss_w = -loss_neg, under autograd for the model, closed form for the weight parameters      :202-203   resample_finetune_loss
+
 There is no CPU fallback: without the HIP library this raises."""
 import collections
 import ctypes as C
@@ -43,6 +49,7 @@ MahaPack = collections.namedtuple("MahaPack", "mean precision W nu")
 MahaRows = collections.namedtuple("MahaRows", "score label y all_scores pooled")
 MahaScores = collections.namedtuple("MahaScores", "score label pooled feats_pt boxes_pt")
 EnergyLoss = collections.namedtuple("EnergyLoss", "loss base reg dlogits energy label")
+ResampleLoss = collections.namedtuple("ResampleLoss", "loss loss_pos loss_neg dlogits row_loss")
 
 
 def score_rows(logits, temperature=1.0, k=0):
@@ -395,3 +402,77 @@ def energy_finetune_loss(logit, target_with_uq, m_in, m_out, weight=0.1, mce_los
     [B]): the forward runs the fused operator once and keeps dlogits, the backward hands `grad_output * dlogits` to the model's autograd boundary."""
     _energy_loss_args("energy_finetune_loss", logit, target_with_uq, weight)
     return _EnergyFinetuneLoss.apply(logit, target_with_uq, float(m_in), float(m_out), float(weight), bool(mce_loss))
+
+
+# ------------------------------------------------------------------------------------------------ soft resampling (tasks/gqa_resampling.py:176-220)
+def _resample_loss_args(name, logits, target_with_uq, n_pos, weights):
+    if not (isinstance(logits, torch.Tensor) and logits.is_cuda and logits.dtype == torch.float32 and logits.dim() == 2):
+        raise ValueError("%s: logits must be a 2-D float32 CUDA tensor" % name)
+    B, NA = logits.shape
+    t = target_with_uq
+    if not (isinstance(t, torch.Tensor) and t.dtype == torch.float32 and t.dim() == 2 and t.device == logits.device and tuple(t.shape) == (B, NA + 1)):
+        raise ValueError("%s: target_with_uq must be a float32 [B, NA + 1] = [%d, %d] tensor on the logits' device, the UQ column last" % (name, B, NA + 1))
+    if not (isinstance(n_pos, int) and not isinstance(n_pos, bool) and 1 <= n_pos < B):
+        raise ValueError("%s: n_pos must be an int with 1 <= n_pos < B = %d (positive rows first, at least one negative row)" % (name, B))
+    w = weights
+    if w is not None and not (isinstance(w, torch.Tensor) and w.dtype == torch.float32 and w.device == logits.device and tuple(w.shape) == (B - n_pos,)):
+        raise ValueError("%s: weights must be a float32 [B - n_pos] = [%d] tensor on the logits' device" % (name, B - n_pos))
+    return (logits if logits.stride(1) == 1 else logits.contiguous()), (t if t.stride(1) == 1 else t.contiguous())
+
+
+def resample_loss_rows(logits, target_with_uq, n_pos, weights, grad_scale=1.0):
+    """gqa_resampling.py:196-202 on given logits of the concatenated batch, one fused pass (`rgqa_op_resample_loss`).  logits: f32 CUDA [B, NA], any row
+    stride, rows [0, n_pos) positive and the rest negative; target_with_uq: f32 [B, NA + 1] as the loader gives it (the UQ column is dropped at :176-177
+    and is not read here); weights: f32 [B - n_pos] (ResampleWeights.batch_weights).  Returns ResampleLoss(loss, loss_pos, loss_neg: 0-dim views of one
+    [3] tensor; dlogits [B, NA] = d loss / d logits * grad_scale; row_loss [B - n_pos] = the negative rows' BCE sums)."""
+    z, t = _resample_loss_args("resample_loss_rows", logits, target_with_uq, n_pos, weights)
+    if weights is None:
+        raise ValueError("resample_loss_rows: weights must be a float32 [B - n_pos] tensor")
+    lib = _lib.load()
+    B, NA = z.shape
+    dev = z.device
+    w = weights.contiguous()
+    n = C.c_size_t()
+    _lib.check(lib.rgqa_resample_scratch_floats(1, B, C.byref(n)))
+    scratch = torch.empty(n.value, dtype=torch.float32, device=dev)
+    loss = torch.empty(3, dtype=torch.float32, device=dev)
+    dl = torch.empty(B, NA, dtype=torch.float32, device=dev)
+    rl = torch.empty(B - n_pos, dtype=torch.float32, device=dev)
+    p = _lib.ptr
+    _lib.check(lib.rgqa_op_resample_loss(p(z), z.stride(0), p(t), t.stride(0), B, n_pos, NA, NA, p(w), float(grad_scale), p(loss), p(dl), dl.stride(0), p(rl), p(scratch),
+                                         _stream(dev)))
+    return ResampleLoss(loss[0], loss[1], loss[2], dl, rl)
+
+
+class _ResampleFinetuneLoss(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, logit, target_with_uq, n_pos, weights):
+        r = resample_loss_rows(logit.detach(), target_with_uq, n_pos, weights)
+        ctx.save_for_backward(r.dlogits)
+        loss_w = -r.loss_neg
+        ctx.mark_non_differentiable(loss_w, r.row_loss)
+        return r.loss.clone(), loss_w, r.row_loss
+
+    @staticmethod
+    def backward(ctx, grad_loss, *unused):
+        dl, = ctx.saved_tensors
+        return grad_loss * dl, None, None, None
+
+
+def resample_finetune_loss(logit, target_with_uq, n_pos, rw, wids):
+    """What a trainer puts in place of gqa_resampling.py:183-203: `loss, loss_w = resample_finetune_loss(model(cat(feats_pos, feats_neg), cat(boxes_pos,
+    boxes_neg), sent_pos + sent_neg), cat(target_pos, target_neg), len(sent_pos), rw, wids)` with the targets as the loader gives them (UQ column
+    last), `rw` a rgqa_amd.resample.ResampleWeights and `wids` the weight-parameter indices of the negative rows (:183).  Then `optim.zero_grad();
+    loss.backward(); clip_grad_norm_; optim.step(); rw.step()`.  logit: the [B, NA] f32 CUDA output of GQAModel / GQAUNITER / GQABUTD.  Returns (loss
+    0-dim, loss_w 0-dim = -loss_neg, not differentiable: rw.step() has the gradient in closed form).  The forward computes the batch weights, runs the
+    fused operator once, keeps dlogits and leaves the negative rows' losses on `rw`; the backward hands `grad_output * dlogits` to the model's autograd
+    boundary."""
+    _resample_loss_args("resample_finetune_loss", logit, target_with_uq, n_pos, None)
+    if not (hasattr(rw, "batch_weights") and hasattr(rw, "step")):
+        raise ValueError("resample_finetune_loss: rw must be a rgqa_amd.resample.ResampleWeights")
+    if len(wids) != logit.shape[0] - n_pos:
+        raise ValueError("resample_finetune_loss: %d indices for %d negative rows" % (len(wids), logit.shape[0] - n_pos))
+    weights = rw.batch_weights(wids)
+    loss, loss_w, row_loss = _ResampleFinetuneLoss.apply(logit, target_with_uq, n_pos, weights)
+    rw.row_loss = row_loss
+    return loss, loss_w
