@@ -49,6 +49,9 @@ typedef struct rgqa_config {
                          [text ; regions] per sample (x_layers = r_layers = 0), pos_dim = 7, state_dict keys `encoder.model.uniter.*`;
                          `boxes` carries the 7-d position features, set_lengths takes the TEXT token counts */
     int32_t emb_dim;  /* BUTD word-embedding size (300) */
+    int32_t conf_branch; /* arch 0 only, default 0: 1 = GQAModel_branched (tasks/gqa_model_branched.py:14-51): a second head conf_fc = Linear(H, 2H) -> GeLU ->
+                            LayerNorm(2H) -> Linear(2H, 1) on the pooled vector.  Six tensors conf_fc.0 / .2 / .3 .weight / .bias follow logit_fc.3 in the parameter
+                            table (conf_fc.3 is read from the f32 master arena); with 0 the table and every result are unchanged */
 } rgqa_config;
 
 typedef struct rgqa_engine rgqa_engine;
@@ -159,6 +162,23 @@ int rgqa_engine_backward(rgqa_engine* e, const float* dlogits, int ld, int accum
  * weight_g and weight_v - the tail of the arena), accumulate = 1 leaves it as it is, so rgqa_engine_backward followed by this call with
  * accumulate = 1 after ONE forward gives the gradient of a loss that reads both outputs.  Honours rgqa_engine_set_input_grads. */
 int rgqa_engine_backward_pooled(rgqa_engine* e, const float* dpooled, int ld, int accumulate, void* stream);
+/* ---- the confidence branch (rgqa_config.conf_branch = 1).  The forward pass also leaves conf_logit [B] f32 = conf_fc(pooled) (the conf_fc.0 GEMM in the
+ * engine's forward precision, GeLU / LayerNorm statistics / the 2H -> 1 dot in f32); rgqa_engine_get_conf copies it out. */
+int rgqa_engine_get_conf(rgqa_engine* e, float* conf_logit_out, void* stream);
+/* backward from dL/dlogits [B, num_answers] f32 (row stride ld) and dL/dconf_logit [B] f32 after ONE forward, in ONE encoder backward pass: the conf head's
+ * share is added to d(pooler pre-tanh) before the encoder's backward starts.  Either gradient may be NULL = zeros.  On an engine without the branch dconf
+ * must be NULL and the call is rgqa_engine_backward.  Honours rgqa_engine_set_input_grads. */
+int rgqa_engine_backward2(rgqa_engine* e, const float* dlogits, int ld, const float* dconf, int accumulate, void* stream);
+/* backward from dL/dconf_logit [B] f32 into the six conf_fc tensors ALONE (the conf_only path below with a caller-supplied gradient: a model whose answer
+ * branch and encoder are frozen under autograd): no answer-head or encoder backward; accumulate = 0 leaves exact zeros everywhere else. */
+int rgqa_engine_backward_conf(rgqa_engine* e, const float* dconf, int accumulate, void* stream);
+/* The train step of the branched trainer (tasks/gqa_branched.py:126-143): rgqa_op_branched_loss (below) on the last forward's logits and conf logits +
+ * backward into the grad arena.  target_with_uq [B, ld_target >= num_answers + 1] f32, column num_answers = the UQ flag (non-zero = unanswerable).
+ * loss3 (3 floats: loss, loss_ce, loss_conf), conf [B] = sigmoid(conf_logit), label [B] int64: device buffers, each may be NULL.  After the call the gradient
+ * arena has the bits of rgqa_engine_backward2 on the operator's dlogits and dconf.  conf_only != 0 (--freeze_vqa_branch): only the six conf_fc tensors receive
+ * gradients - neither the answer head's nor the encoder's backward is launched; accumulate = 0 then leaves exact zeros everywhere else. */
+int rgqa_engine_branched_loss_backward(rgqa_engine* e, const float* target_with_uq, int ld_target, int mce, float grad_scale, int conf_only, float* loss3,
+                                       float* conf, int64_t* label, int accumulate, void* stream);
 /* debug / parity: copy a saved activation ("embed_lang", "embed_visn", "l3", "r1", "x2_lang", "x2_visn", "pooled") as f32 */
 int rgqa_engine_get_activation(rgqa_engine* e, const char* name, float* out, size_t cap_elems, void* stream);
 /* Cross-attention probabilities of cross-modality layer `layer` after a forward pass (reference lxrt_vis/modeling.py:337,
@@ -416,6 +436,17 @@ int rgqa_op_attention_rows(const void* q, int ldq, const void* kv, int ldkv, con
 int rgqa_op_attention_rows_bwd(const void* q, int ldq, const void* kv, int ldkv, const int* cu_q, const int* cu_k, const float* mask, const float* lse,
                                const void* dout, void* dq, void* dkv, int B, int nh, int Lq, int Lk, int dtype, int impl, void* stream);
 int rgqa_op_bce(const float* logits, const float* target, float* loss, float* dlogits, int B, int NA, void* stream);
+/* The loss head of the branched trainer (tasks/gqa_branched.py:126-143, :147, :209-210; rgqa_amd/csrc/branched_loss.hip), one pass per row.  With n_id
+ * answerable rows (UQ flag = target_with_uq[b * ld_target + NA] == 0): loss_ce = BCE-with-logits summed over the answers, averaged over the answerable rows
+ * (mce: cross entropy at the first maximum of the target row, x NA); loss_conf = mean_b BCE(sigmoid(conf_logit_b), id_b) in the softplus form max(c, 0) - c id +
+ * log1p(exp(-|c|)), each term capped at 100; dlogits [B, NAp] f32 = (sigmoid(z) - t) / n_id (mce: (NA / n_id)(softmax(z) - onehot)) on the answerable rows, exact
+ * zeros on the others and in columns NA .. NAp; dconf_b = (sigmoid(c_b) - id_b) / B; both times grad_scale.  Outputs loss3 (loss, loss_ce, loss_conf), dlogits,
+ * dconf [B], conf [B] = sigmoid(conf_logit), label [B] int64 (first maximum of the logit row), score1 [B] = max sigmoid(logit) may each be NULL; loss3 needs
+ * `scratch` of rgqa_op_branched_loss_scratch_floats(B) floats.  No answerable row: loss_ce is NaN (0 / 0, as torch's mean over nothing), gradients are finite. */
+int rgqa_op_branched_loss_scratch_floats(int B, size_t* out);
+int rgqa_op_branched_loss(const float* logits, int ld, const float* conf_logit, const float* target_with_uq, int ld_target, int B, int NA, int NAp, int mce,
+                          float grad_scale, float* loss3, float* dlogits, int ldd, float* dconf, float* conf, int64_t* label, float* score1, float* scratch,
+                          void* stream);
 /* The loss head of the energy fine-tuning (tasks/gqa_energy.py:122-138, :144-145; rgqa_amd/csrc/energy_loss.hip), one pass per row:
  *   base  = BCEWithLogitsLoss()(logit, target) * NA, E_b = log(1 + exp(logit_b)).sum()                   (mce = 0; :133-135)
  *         = CrossEntropyLoss()(logit, target.max(1)[1]) * NA, E_b = logsumexp(logit_b)                    (mce != 0, --mceLoss; :128-131)

@@ -11,7 +11,7 @@ PREC_F32, PREC_BF16, PREC_BF16X3, PREC_BF16X3_FWD = 0, 1, 2, 3
 class Config(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("vocab_size", "hidden", "heads", "inter", "max_pos", "type_vocab", "l_layers",
                                          "x_layers", "r_layers", "feat_dim", "pos_dim", "num_answers", "precision")] + \
-               [("ln_eps", C.c_float), ("hidden_dropout", C.c_float), ("attn_dropout", C.c_float), ("arch", C.c_int32), ("emb_dim", C.c_int32)]
+               [("ln_eps", C.c_float), ("hidden_dropout", C.c_float), ("attn_dropout", C.c_float), ("arch", C.c_int32), ("emb_dim", C.c_int32), ("conf_branch", C.c_int32)]
 
 
 _vp, _sz, _i, _f, _u64 = C.c_void_p, C.c_size_t, C.c_int, C.c_float, C.c_uint64
@@ -40,6 +40,10 @@ SIGNATURES = {
     "rgqa_engine_resample_loss_backward": [_vp, _vp, _i, _i, _vp, _f, _vp, _vp, _i, _vp],
     "rgqa_engine_backward": [_vp, _vp, _i, _i, _vp],
     "rgqa_engine_backward_pooled": [_vp, _vp, _i, _i, _vp],
+    "rgqa_engine_get_conf": [_vp, _vp, _vp],
+    "rgqa_engine_backward2": [_vp, _vp, _i, _vp, _i, _vp],
+    "rgqa_engine_backward_conf": [_vp, _vp, _i, _vp],
+    "rgqa_engine_branched_loss_backward": [_vp, _vp, _i, _i, _f, _i, _vp, _vp, _vp, _i, _vp],
     "rgqa_engine_get_activation": [_vp, C.c_char_p, _vp, _sz, _vp],
     "rgqa_engine_get_cross_attention": [_vp, _i, _i, _vp, _sz, _vp],
     "rgqa_engine_set_lengths": [_vp, _vp, _i],
@@ -91,6 +95,8 @@ SIGNATURES = {
     "rgqa_op_bce": [_vp, _vp, _vp, _vp, _i, _i, _vp],
     "rgqa_op_energy_loss_scratch_floats": [_i, C.POINTER(_sz)],
     "rgqa_op_energy_loss": [_vp, _i, _vp, _i, _vp, _i, _i, _i, _i, _i, _f, _f, _f, _f, _vp, _vp, _i, _vp, _vp, _vp, _vp],
+    "rgqa_op_branched_loss_scratch_floats": [_i, C.POINTER(_sz)],
+    "rgqa_op_branched_loss": [_vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _f, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp],
     "rgqa_resample_scratch_floats": [_i, _i, C.POINTER(_sz)],
     "rgqa_resample_weights": [_vp, _i, _vp, _i, _vp, _vp, _vp, _vp],
     "rgqa_op_resample_loss": [_vp, _i, _vp, _i, _i, _i, _i, _i, _vp, _f, _vp, _vp, _i, _vp, _vp, _vp],

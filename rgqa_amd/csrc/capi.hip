@@ -65,6 +65,8 @@ int rgqa_debug_set(int key, int value) {
 
 int rgqa_engine_create(const rgqa_config* cfg, rgqa_engine** out) {
     RGQA_REQUIRE(cfg != nullptr && out != nullptr, "engine_create: null argument");
+    RGQA_REQUIRE(cfg->conf_branch == 0 || cfg->conf_branch == 1, "engine_create: conf_branch must be 0 or 1 (got %d)", cfg->conf_branch);
+    RGQA_REQUIRE(cfg->conf_branch == 0 || cfg->arch == 0, "engine_create: the confidence branch (conf_branch = 1) exists on the LXMERT engine only (arch 0); got arch %d", cfg->arch);
     if (cfg->arch == 1) {
         RGQA_REQUIRE(cfg->hidden > 0 && cfg->hidden % 64 == 0 && cfg->emb_dim > 0 && cfg->vocab_size > 1 && cfg->num_answers > 0 && cfg->feat_dim % 4 == 0 &&
                      cfg->pos_dim >= 1 && cfg->pos_dim <= 4, "engine_create (BUTD): hidden %% 64, emb_dim, vocab_size, num_answers, feat_dim %% 4 required");
@@ -157,6 +159,25 @@ int rgqa_engine_resample_loss_backward(rgqa_engine* e, const float* target, int 
 int rgqa_engine_backward(rgqa_engine* e, const float* dlogits, int ld, int accumulate, void* stream) {
     NEED(e);
     return e->impl->backward(dlogits, ld, accumulate, S(stream));
+}
+int rgqa_engine_get_conf(rgqa_engine* e, float* conf_logit_out, void* stream) {
+    NEED(e);
+    RGQA_REQUIRE(conf_logit_out != nullptr, "get_conf: null argument");
+    return e->impl->get_conf(conf_logit_out, S(stream));
+}
+int rgqa_engine_backward2(rgqa_engine* e, const float* dlogits, int ld, const float* dconf, int accumulate, void* stream) {
+    NEED(e);
+    return e->impl->backward2(dlogits, ld, dconf, accumulate, S(stream));
+}
+int rgqa_engine_backward_conf(rgqa_engine* e, const float* dconf, int accumulate, void* stream) {
+    NEED(e);
+    return e->impl->backward_conf(dconf, accumulate, S(stream));
+}
+int rgqa_engine_branched_loss_backward(rgqa_engine* e, const float* target_with_uq, int ld_target, int mce, float grad_scale, int conf_only, float* loss3,
+                                       float* conf, int64_t* label, int accumulate, void* stream) {
+    NEED(e);
+    RGQA_REQUIRE(target_with_uq != nullptr, "branched_loss_backward: null target");
+    return e->impl->branched_loss_backward(target_with_uq, ld_target, mce ? 1 : 0, grad_scale, conf_only ? 1 : 0, loss3, conf, label, accumulate, S(stream));
 }
 int rgqa_engine_backward_pooled(rgqa_engine* e, const float* dpooled, int ld, int accumulate, void* stream) {
     NEED(e);
@@ -470,6 +491,16 @@ int rgqa_op_energy_loss(const float* logits, int ld, const float* target, int ld
                         float m_in, float m_out, float grad_scale, float* loss3, float* dlogits, int ldd, float* energy, int64_t* label, float* scratch, void* stream) {
     const EnergyLossCfg c = {mce ? 1 : 0, weight, m_in, m_out};
     return k_energy_loss(logits, ld, target, ld_target, ood_flag, ld_flag, B, NA, NAp, c, grad_scale, loss3, dlogits, ldd, energy, label, scratch, S(stream));
+}
+int rgqa_op_branched_loss_scratch_floats(int B, size_t* out) {
+    RGQA_REQUIRE(B > 0 && out != nullptr, "op_branched_loss_scratch_floats: bad argument");
+    *out = k_branched_loss_scratch_floats(B);
+    return RGQA_OK;
+}
+int rgqa_op_branched_loss(const float* logits, int ld, const float* conf_logit, const float* target_with_uq, int ld_target, int B, int NA, int NAp, int mce,
+                          float grad_scale, float* loss3, float* dlogits, int ldd, float* dconf, float* conf, int64_t* label, float* score1, float* scratch,
+                          void* stream) {
+    return k_branched_loss(logits, ld, conf_logit, target_with_uq, ld_target, B, NA, NAp, mce, grad_scale, loss3, dlogits, ldd, dconf, conf, label, score1, scratch, S(stream));
 }
 int rgqa_resample_scratch_floats(int N, int B, size_t* out) {
     RGQA_REQUIRE(N > 0 && B > 0 && out != nullptr, "resample_scratch_floats: bad argument");

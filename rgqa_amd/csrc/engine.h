@@ -116,6 +116,17 @@ public:
     virtual int resample_loss_backward(const float* target, int ldt, int n_pos, const float* weights, float grad_scale, float* loss3, float* row_loss, int accumulate,
                                        hipStream_t s) = 0;
     virtual int backward(const float* dlogits, int ldd, int accumulate, hipStream_t s) = 0;
+    // the confidence branch (rgqa_config.conf_branch = 1; engine.hip): conf logits of the last forward [B]; backward from dlogits and dconf (either may be null =
+    // zeros) in ONE pass; the loss head of the branched trainer (branched_loss.hip) + that backward (conf_only: the six conf_fc tensors alone)
+    virtual int get_conf(float*, hipStream_t) { rgqa_set_error("get_conf: this engine has no confidence branch (rgqa_config.conf_branch)"); return RGQA_ERR_ARG; }
+    virtual int backward2(const float* dlogits, int ldd, const float* dconf, int accumulate, hipStream_t s) {
+        if (dconf != nullptr || dlogits == nullptr) { rgqa_set_error("backward2: this engine has no confidence branch (rgqa_config.conf_branch)"); return RGQA_ERR_ARG; }
+        return backward(dlogits, ldd, accumulate, s);
+    }
+    virtual int backward_conf(const float*, int, hipStream_t) { rgqa_set_error("backward_conf: this engine has no confidence branch (rgqa_config.conf_branch)"); return RGQA_ERR_ARG; }
+    virtual int branched_loss_backward(const float*, int, int, float, int, float*, float*, int64_t*, int, hipStream_t) {
+        rgqa_set_error("branched_loss_backward: this engine has no confidence branch (rgqa_config.conf_branch)"); return RGQA_ERR_ARG;
+    }
     virtual int backward_pooled(const float* dpooled, int ld, int accumulate, hipStream_t s) = 0;
     // gradient-arena ranges in the order backward finishes them (for overlapping the DP exchange with backward)
     struct GradSeg { size_t begin, end; int event; };

@@ -18,6 +18,7 @@ struct ModelParams {
     std::vector<AttP> l_att, r_att; std::vector<FfnP> l_ffn, r_ffn;
     std::vector<AttP> x_cross, x_latt, x_vatt; std::vector<FfnP> x_lffn, x_vffn;
     Lin pooler, head0; LNp head_ln; Lin head3;
+    Lin conf0; LNp conf_ln; Lin conf3;      // conf_branch: conf_fc.0 / .2 / .3 (tasks/gqa_model_branched.py:28-33)
 };
 
 struct TableBuilder {
@@ -142,6 +143,15 @@ static void build_params(const rgqa_config& c, std::vector<ParamInfo>& tab, Mode
     mp.head0 = tb.lin("logit_fc.0", 2 * H, H);
     mp.head_ln = tb.ln("logit_fc.2", 2 * H);
     mp.head3 = tb.lin("logit_fc.3", c.num_answers, 2 * H);
+    if (c.conf_branch) {
+        // behind the answer head, inside the head + pooler gradient segment (build_grad_segments: [pooler, end of the arena))
+        mp.conf0 = tb.lin("conf_fc.0", 2 * H, H);
+        mp.conf_ln = tb.ln("conf_fc.2", 2 * H);
+        // one output row: a row dot product on the f32 masters (conf_head.hip), no operand copies and no [2H, 64] transposed slot
+        mp.conf3.out = 1; mp.conf3.in = 2 * H; mp.conf3.ldt = 64;
+        mp.conf3.w = tb.add("conf_fc.3.weight", 1, 2 * H, 2, 0, 1); tb.read_as_f32(mp.conf3.w);
+        mp.conf3.b = tb.add("conf_fc.3.bias", 1, 0, 1, 64, 0);
+    }
     total = rup(tb.cur, 64);
 }
 
@@ -268,6 +278,10 @@ public:
     T *zf = nullptr, *visn_out = nullptr, *feats_lp = nullptr; float* visn_stats = nullptr;
     T *pooled = nullptr, *h1pre = nullptr, *h1 = nullptr, *h2 = nullptr; float *hd_mean = nullptr, *hd_rstd = nullptr;
     float* logits = nullptr; TB* dlogits = nullptr; float* loss_dev = nullptr;
+    // confidence branch: gelu'(pre) and gelu(pre) of conf_fc.0, the LayerNorm statistics, the conf logits; backward: the gradient entering conf_fc.0's output,
+    // its share of d(pooler pre-tanh), dL/dconf_logit of the pass being run (dconf_ready: an entry point filled it; otherwise zeros)
+    T *c1dg = nullptr, *c1 = nullptr; float *cf_mean = nullptr, *cf_rstd = nullptr, *conf_logit = nullptr;
+    TB *gc3 = nullptr, *gcp = nullptr; float* dconf_dev = nullptr; bool dconf_ready = false;
     TB *gA = nullptr, *gB = nullptr, *gctx = nullptr;
     TB *gz_s[NPAR][3] = {}, *gzd_s[NPAR][3] = {}, *gqkv_s[NPAR][3] = {}, *gh_s[NPAR][3] = {};   // [ring position of the launch period][stage slot]
     hipStream_t s_w = nullptr;                 // side stream: the deferred weight-gradient GEMMs of a layer run beside the next layer's chain
@@ -488,6 +502,7 @@ public:
         for (auto& f : mp.x_lffn) addffn(f);
         for (auto& f : mp.x_vffn) addffn(f);
         add(mp.pooler); add(mp.head0); add(mp.head3);
+        if (cfg.conf_branch) add(mp.conf0);
         n_tdesc = (int)tdesc_host.size();
         n_tdesc_min = (int)tdesc_min_host.size();
     }
@@ -584,6 +599,10 @@ public:
         pooled = take<T>((size_t)B * H); h1pre = take<T>((size_t)B * 2 * H); h1 = take<T>((size_t)B * 2 * H); h2 = take<T>((size_t)B * 2 * H);
         hd_mean = take<float>(B); hd_rstd = take<float>(B);
         logits = take<float>((size_t)B * NAp);
+        if (cfg.conf_branch) {
+            c1dg = take<T>((size_t)B * 2 * H); c1 = take<T>((size_t)B * 2 * H);
+            cf_mean = take<float>(B); cf_rstd = take<float>(B); conf_logit = take<float>(B);
+        }
         if (joint) {      // UNITER front-end: its forward tensors (they have bf16 images under MIXED) before the mark below
             const size_t ni = (size_t)B * Oi;
             u_zf = take<T>(ni * H); u_zp = take<T>(ni * H); u_a1 = take<T>(ni * H); u_a2 = take<T>(ni * H); u_x3 = take<T>(ni * H);
@@ -609,6 +628,7 @@ public:
                 gqkv_s[par][k] = take<TB>((size_t)RC * 3 * H); gh_s[par][k] = take<TB>((size_t)RC * I);
             }
         gp1 = take<TB>((size_t)B * 2 * H); gp2 = take<TB>((size_t)B * 2 * H); gp3 = take<TB>((size_t)B * 2 * H);
+        if (cfg.conf_branch) { gc3 = take<TB>((size_t)B * 2 * H); gcp = take<TB>((size_t)B * H); dconf_dev = take<float>(B); }
         size_t pw = 2 * (size_t)H; if ((size_t)I > pw) pw = I; if (3 * (size_t)H > pw) pw = 3 * (size_t)H; if ((size_t)NAp > pw) pw = NAp;
         part_floats = (size_t)512 * 10 * pw;
         part = take<float>(part_floats);
@@ -1126,6 +1146,13 @@ public:
             // logits columns come out as exact zeros and the GEMM runs on the LDS-DMA kernel
             add_fwd(g, h2, 2 * H, mp.head3, 0, LP ? NAp : cfg.num_answers, logits, NAp, B, EPI_BIAS, nullptr, 0, nullptr, 0);
             CK(run_fwd(g, s, 1, 0, true));
+            if (cfg.conf_branch) {
+                // a launch of its own behind the answer head's: the head's launches stay what the plain engine issues, bit for bit
+                gg_init(g);
+                add_fwd(g, pooled, H, mp.conf0, 0, 2 * H, c1, 2 * H, B, EPI_GELU, nullptr, 0, c1dg, 0);
+                CK(run_fwd(g, s, 0, 0, true));
+                CKP(PC_LN, k_conf_tail_fwd<T>(c1, 2 * H, P + mp.conf_ln.w, P + mp.conf_ln.b, P + mp.conf3.w, P + mp.conf3.b, conf_logit, cf_mean, cf_rstd, B, 2 * H, cfg.ln_eps, s));
+            }
         }
         if (pooled_out) CKP(PC_OTHER, k_to_f32<T>(pooled, H, pooled_out, H, B, H, s));
         if (logits_out) CKP(PC_OTHER, k_fill_rows<float>(logits_out, ld_logits, logits, NAp, B, cfg.num_answers, s));
@@ -1174,6 +1201,81 @@ public:
         CKP(PC_OTHER, k_cast_pad<TB>(dl, ldd, dlogits, NAp, B, cfg.num_answers, 1.0f, s));
         return backward_impl(accumulate, s);
     }
+    // ---- confidence branch
+    int get_conf(float* out, hipStream_t s) override {
+        RGQA_REQUIRE(cfg.conf_branch, "get_conf: this engine has no confidence branch (rgqa_config.conf_branch)");
+        RGQA_REQUIRE(have_fwd, "get_conf: no forward pass recorded");
+        return rgqa_check_hip(hipMemcpyAsync(out, conf_logit, sizeof(float) * B, hipMemcpyDeviceToDevice, s), "conf copy");
+    }
+    int backward2(const float* dl, int ldd, const float* dconf, int accumulate, hipStream_t s) override {
+        RGQA_REQUIRE(have_fwd, "backward2: no forward pass recorded");
+        RGQA_REQUIRE(G != nullptr, "backward2: no gradient arena bound");
+        RGQA_REQUIRE(cfg.conf_branch || dconf == nullptr, "backward2: dconf given to an engine without the confidence branch (rgqa_config.conf_branch)");
+        RGQA_REQUIRE(cfg.conf_branch || dl != nullptr, "backward2: null dlogits");
+        prof_block = PB_HEAD;
+        if (dl) CKP(PC_OTHER, k_cast_pad<TB>(dl, ldd, dlogits, NAp, B, cfg.num_answers, 1.0f, s));
+        else CK(rgqa_check_hip(hipMemsetAsync(dlogits, 0, (size_t)B * NAp * sizeof(TB), s), "zero dlogits"));
+        if (cfg.conf_branch) {
+            if (dconf) CK(rgqa_check_hip(hipMemcpyAsync(dconf_dev, dconf, sizeof(float) * B, hipMemcpyDeviceToDevice, s), "dconf copy"));
+            else CK(rgqa_check_hip(hipMemsetAsync(dconf_dev, 0, sizeof(float) * B, s), "zero dconf"));
+            dconf_ready = true;
+        }
+        return backward_impl(accumulate, s);
+    }
+    // conf_only from a caller-supplied dL/dconf_logit (autograd integration of a model whose answer branch and encoder are frozen)
+    int backward_conf(const float* dconf, int accumulate, hipStream_t s) override {
+        RGQA_REQUIRE(cfg.conf_branch, "backward_conf: this engine has no confidence branch (rgqa_config.conf_branch)");
+        RGQA_REQUIRE(have_fwd, "backward_conf: no forward pass recorded");
+        RGQA_REQUIRE(G != nullptr && dconf != nullptr, "backward_conf: null gradient arena / dconf");
+        CK(rgqa_check_hip(hipMemcpyAsync(dconf_dev, dconf, sizeof(float) * B, hipMemcpyDeviceToDevice, s), "dconf copy"));
+        dconf_ready = true;
+        return backward_conf_only(accumulate, s);
+    }
+    int branched_loss_backward(const float* target_uq, int ldt, int mce, float grad_scale, int conf_only, float* loss3, float* conf, int64_t* label, int accumulate,
+                               hipStream_t s) override {
+        RGQA_REQUIRE(cfg.conf_branch, "branched_loss_backward: this engine has no confidence branch (rgqa_config.conf_branch)");
+        RGQA_REQUIRE(have_fwd, "branched_loss_backward: no forward pass recorded");
+        RGQA_REQUIRE(G != nullptr, "branched_loss_backward: no gradient arena bound");
+        prof_block = PB_HEAD;
+        float* dl32 = part;   // as loss_backward: [B, NAp] f32, the row shares of the loss behind it
+        RGQA_REQUIRE((size_t)B * NAp + k_branched_loss_scratch_floats(B) <= part_floats, "branched_loss_backward: batch %d exceeds the scratch", B);
+        CKP(PC_OTHER, k_branched_loss(logits, NAp, conf_logit, target_uq, ldt, B, cfg.num_answers, NAp, mce, grad_scale, loss3, conf_only ? nullptr : dl32, NAp, dconf_dev,
+                                      conf, label, nullptr, part + (size_t)B * NAp, s));
+        dconf_ready = true;
+        if (conf_only) return backward_conf_only(accumulate, s);
+        CKP(PC_OTHER, k_cast_pad<TB>(dl32, NAp, dlogits, NAp, B, NAp, 1.0f, s));
+        return backward_impl(accumulate, s);
+    }
+    // The conf head's backward from dconf_dev: the gradients of conf_fc.2 / .3 and conf_fc.0.bias now; with_encoder: conf_fc.0's weight gradient joins the head's
+    // deferred group and its share of d(pooler pre-tanh) is added to gp1 (which backward_impl has just written) - ONE encoder backward follows;
+    // otherwise (conf_only) the weight gradient is launched here and nothing flows on.
+    int conf_backward(int accumulate, bool with_encoder, hipStream_t s) {
+        const int H = cfg.hidden;
+        CKP(PC_LN, k_conf_tail_bwd<TB>(dconf_dev, sv(c1), sv(c1dg), 2 * H, P + mp.conf_ln.w, P + mp.conf_ln.b, P + mp.conf3.w, cf_mean, cf_rstd, gc3, 2 * H,
+                                       G + mp.conf_ln.w, G + mp.conf_ln.b, G + mp.conf3.w, G + mp.conf3.b, accumulate, B, 2 * H, s));
+        dconf_ready = false;
+        CKP(PC_OTHER, colsum_bias(gc3, 2 * H, mp.conf0, 0, 2 * H, B, accumulate, s));
+        GemmGroup g; gg_init(g);
+        if (!with_encoder) {
+            add_wgrad(g, gc3, 2 * H, mp.conf0, 0, 2 * H, sv(pooled), H, B, accumulate);
+            return run_wgrad(g, s);
+        }
+        add_wgrad(wg_head, gc3, 2 * H, mp.conf0, 0, 2 * H, sv(pooled), H, B, accumulate);
+        add_dgrad(g, gc3, 2 * H, mp.conf0, 0, 2 * H, gcp, H, B, EPI_DTANH, sv(pooled), H); CK(run_dgrad(g, s, true));
+        CKP(PC_OTHER, k_add_inplace<TB>(gp1, gcp, (size_t)B * H, s));
+        return RGQA_OK;
+    }
+    // --freeze_vqa_branch (tasks/gqa_branched.py:80-83): only conf_fc is trained - the loss needs neither the answer head's nor the encoder's backward
+    int backward_conf_only(int accumulate, hipStream_t s) {
+        prof_block = PB_HEAD;
+        CK(wait_bwd(s));
+        if (!accumulate) CK(rgqa_check_hip(hipMemsetAsync(G, 0, sizeof(float) * mp.conf0.w, s), "zero the gradients below conf_fc"));
+        CK(conf_backward(accumulate, false, s));
+        // every gradient segment is final on this stream: its event and its share of the clip norm, as after a full pass
+        seg_cursor = 0;
+        for (int k = 0; k < n_seg_events; ++k) CK(mark_segment(s));
+        return RGQA_OK;
+    }
 
     int colsum_bias(const void* dy, int ld, const Lin& l, int col0, int cols, int M, int accumulate, hipStream_t s) {
         return k_colsum<TB>((const TB*)dy + col0, ld, part, G + l.b + col0, accumulate, M, cols, s);
@@ -1205,6 +1307,10 @@ public:
         CKP(PC_OTHER, colsum_bias(gp3, 2 * H, mp.head0, 0, 2 * H, B, accumulate, s));
         add_wgrad(wg_head, gp3, 2 * H, mp.head0, 0, 2 * H, sv(pooled), H, B, accumulate);
         gg_init(g); add_dgrad(g, gp3, 2 * H, mp.head0, 0, 2 * H, gp1, H, B, EPI_DTANH, sv(pooled), H); CK(run_dgrad(g, s, true));   // gp1[B,H] = d(pooler pre-tanh)
+        if (cfg.conf_branch) {
+            if (!dconf_ready) CK(rgqa_check_hip(hipMemsetAsync(dconf_dev, 0, sizeof(float) * B, s), "zero dconf"));      // an entry point that knows no dconf: zeros
+            CK(conf_backward(accumulate, true, s));
+        }
         return backward_encoder(accumulate, s);
     }
 

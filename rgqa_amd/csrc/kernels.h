@@ -198,6 +198,26 @@ size_t k_energy_loss_scratch_floats(int B);
 int k_energy_loss(const float* logits, int ld, const float* target, int ldt, const float* ood_flag, int ldf, int B, int NA, int NAp, const EnergyLossCfg& c, float grad_scale,
                   float* loss3, float* dlogits, int ldd, float* energy, int64_t* label, float* scratch, hipStream_t s);
 
+// ---- branched_loss.hip: the loss head of the confidence-branch trainer (tasks/gqa_branched.py:126-143, :147, :209-210) in one pass per row
+size_t k_branched_loss_scratch_floats(int B);
+// target_with_uq [B, >= NA + 1]: column NA is the UQ flag (non-zero = unanswerable).  Outputs, each may be null: loss3 = {loss, loss_ce, loss_conf} (needs `scratch`,
+// k_branched_loss_scratch_floats(B) floats), dlogits [B, NAp] f32 (unanswerable rows and columns NA .. NAp exact zeros), dconf [B], conf [B] = sigmoid(conf_logit),
+// label [B] = first maximum of the logit row, score1 [B] = max sigmoid(logit)
+int k_branched_loss(const float* logits, int ld, const float* conf_logit, const float* target_with_uq, int ldt, int B, int NA, int NAp, int mce, float grad_scale,
+                    float* loss3, float* dlogits, int ldd, float* dconf, float* conf, int64_t* label, float* score1, float* scratch, hipStream_t s);
+
+// ---- conf_head.hip: the confidence branch behind its conf_fc.0 GEMM (tasks/gqa_model_branched.py:28-33): LayerNorm + the 2H -> 1 projection as a row dot product
+// x = gelu(pre) [B, N]; conf[b] = LN(x_b) . w3 + b3[0]; mean / rstd [B] kept for the backward
+template <typename T>
+int k_conf_tail_fwd(const T* x, int ld, const float* gamma, const float* beta, const float* w3, const float* b3, float* conf, float* mean, float* rstd, int B, int N,
+                    float eps, hipStream_t s);
+// gc [B, N] = the gradient entering conf_fc.0's output (dgelu = gelu'(pre), what the EPI_GELU epilogue saved); dgamma / dbeta / dw3 [N], db3 [1] summed over the
+// rows in a fixed order
+template <typename T>
+int k_conf_tail_bwd(const float* dconf, const T* x, const T* dgelu, int ld, const float* gamma, const float* beta, const float* w3, const float* mean, const float* rstd,
+                    T* gc, int ldg, float* dgamma, float* dbeta, float* dw3, float* db3, int accumulate, int B, int N, hipStream_t s);
+template <typename T> int k_add_inplace(T* a, const T* b, size_t n, hipStream_t s);
+
 // ---- resample.hip: the step of the soft resampling of the unanswerable questions (tasks/gqa_resampling.py:176-220): batch weights from the N weight
 // parameters, the row-weighted BCE head, and the closed-form gradient of the weight parameters with its SGD-momentum update
 size_t k_resample_scratch_floats(int N, int B);      // what any of the three calls below needs (N = 0: the loss call alone)

@@ -77,7 +77,7 @@ class Engine:
 
     def __init__(self, vocab_size=30522, hidden=768, heads=12, inter=3072, max_pos=512, type_vocab=2, l_layers=9,
                  x_layers=5, r_layers=5, feat_dim=2048, pos_dim=4, num_answers=1842, precision="bf16",
-                 ln_eps=1e-12, hidden_dropout=0.1, attn_dropout=0.1, arch=0, emb_dim=300):
+                 ln_eps=1e-12, hidden_dropout=0.1, attn_dropout=0.1, arch=0, emb_dim=300, conf_branch=False):
         self.lib = _lib.load()
         self.precision = precision
         # "bf16x3": split-f32 operands, three bf16 MFMA products per f32 product - the fast mode inside the reference's 1e-3 logits bound;
@@ -87,7 +87,9 @@ class Engine:
         self.precision = precision
         prec = {"bf16": PREC_BF16, "f32": PREC_F32, "bf16x3": PREC_BF16X3, "bf16x3_fwd": PREC_BF16X3_FWD}[precision]
         self.cfg = Config(vocab_size, hidden, heads, inter, max_pos, type_vocab, l_layers, x_layers, r_layers, feat_dim,
-                          pos_dim, num_answers, prec, ln_eps, hidden_dropout, attn_dropout, arch, emb_dim)
+                          pos_dim, num_answers, prec, ln_eps, hidden_dropout, attn_dropout, arch, emb_dim, 1 if conf_branch else 0)
+        # conf_branch: the reference's GQAModel_branched (tasks/gqa_model_branched.py:14-51) - six conf_fc tensors behind logit_fc.3, `conf_logit` after forward
+        self.conf_branch = bool(conf_branch)
         h = C.c_void_p()
         check(self.lib.rgqa_engine_create(C.byref(self.cfg), C.byref(h)))
         self.h = h
@@ -210,6 +212,8 @@ class Engine:
         self._io = dict(logits=torch.empty(B, na, dtype=torch.float32, device=self.device),
                         pooled=torch.empty(B, H, dtype=torch.float32, device=self.device),
                         loss=torch.zeros(1, dtype=torch.float32, device=self.device))
+        if self.conf_branch:
+            self._io["conf_logit"] = torch.empty(B, dtype=torch.float32, device=self.device)
 
     def sync_weights(self):
         """Refreshes the operand copies of the weights (direct + transposed; bf16 or split f32) from the f32 master arena."""
@@ -253,6 +257,8 @@ class Engine:
         lg, pl = self._io["logits"], self._io["pooled"]
         check(self.lib.rgqa_engine_forward(self.h, ptr(feats), ptr(boxes), ptr(input_ids), ptr(segment_ids), ptr(input_mask),
                                            ptr(pl), ptr(lg), lg.stride(0), 1 if train else 0, C.c_uint64(seed), _stream()))
+        if self.conf_branch:
+            check(self.lib.rgqa_engine_get_conf(self.h, ptr(self._io["conf_logit"]), _stream()))
         for k in [k for k in self._wev_refs if k != "bwd"]:      # the waits are enqueued: the one-shot weight events may go
             del self._wev_refs[k]
         self.join_update()      # an optimizer pass beside this forward (it finished long ago: 1.3 ms against 3.6): whatever follows on this stream sees its results
@@ -342,11 +348,78 @@ class Engine:
         """[3] device tensor of the last resample_loss_backward: loss, loss_pos, loss_neg (None before the first call)"""
         return self._io.get("rs_loss3")
 
-    def backward(self, dlogits, accumulate=False):
-        dlogits = dlogits.contiguous().float()
-        check(self.lib.rgqa_engine_backward(self.h, ptr(dlogits), dlogits.stride(0), 1 if accumulate else 0, _stream()))
+    def backward(self, dlogits, accumulate=False, dconf=None):
+        """Backward from dL/dlogits [B, num_answers].  On an engine with the confidence branch: `dconf` = dL/dconf_logit ([B] or [B, 1]); either gradient
+        may be None (= zeros), and whatever combination arrives is ONE encoder backward pass (rgqa_engine_backward2)."""
+        if not self.conf_branch:
+            if dconf is not None:
+                raise ValueError("backward: dconf given to an engine without the confidence branch (conf_branch=True)")
+            dlogits = dlogits.contiguous().float()
+            check(self.lib.rgqa_engine_backward(self.h, ptr(dlogits), dlogits.stride(0), 1 if accumulate else 0, _stream()))
+        else:
+            if dlogits is None and dconf is None:
+                raise ValueError("backward: both gradients are None")
+            if dlogits is not None:
+                dlogits = dlogits.contiguous().float()
+            if dconf is not None:
+                dconf = dconf.reshape(-1).contiguous().float()
+                if dconf.numel() != self.shape[0]:
+                    raise ValueError("dconf must hold B = %d elements; got %d" % (self.shape[0], dconf.numel()))
+            check(self.lib.rgqa_engine_backward2(self.h, ptr(dlogits), dlogits.stride(0) if dlogits is not None else 0, ptr(dconf),
+                                                 1 if accumulate else 0, _stream()))
         self._wev_refs.pop("bwd", None)
         self._seg_sumsq_valid = self._seg_sumsq is not None
+
+    def backward_conf_only(self, dconf, accumulate=False):
+        """dL/dconf_logit ([B] or [B, 1]) into the six conf_fc tensors alone: no answer-head or encoder backward, exact zeros elsewhere (accumulate=False)"""
+        if not self.conf_branch:
+            raise RuntimeError("backward_conf_only: this engine has no confidence branch (Engine(conf_branch=True))")
+        dconf = dconf.reshape(-1).contiguous().float()
+        if dconf.numel() != self.shape[0]:
+            raise ValueError("dconf must hold B = %d elements; got %d" % (self.shape[0], dconf.numel()))
+        check(self.lib.rgqa_engine_backward_conf(self.h, ptr(dconf), 1 if accumulate else 0, _stream()))
+        self._wev_refs.pop("bwd", None)
+        self._seg_sumsq_valid = self._seg_sumsq is not None
+
+    @property
+    def conf_logit(self):
+        """[B] f32 conf logits of the last forward (engine-owned, overwritten by the next call); None without the confidence branch"""
+        return self._io.get("conf_logit")
+
+    def branched_loss_backward(self, target_with_uq, mce=False, grad_scale=1.0, conf_only=False, accumulate=False):
+        """The train step of the reference's branched trainer (tasks/gqa_branched.py:126-143) on the last forward's logits and conf logits: answer loss over
+        the answerable rows (BCE x NA, or with mce=True cross entropy x NA at the first maximum of the target row) + BCE(sigmoid(conf), answerable flag), and
+        backward into the gradient arena in ONE encoder pass.  target_with_uq [B, num_answers + 1] f32: the last column is the UQ flag (non-zero =
+        unanswerable), read in place.  conf_only=True is --freeze_vqa_branch: only the six conf_fc tensors receive gradients, no answer-head or encoder
+        backward is launched, the rest of the arena is exact zeros (accumulate=False).  Returns (loss [1], conf [B] = sigmoid(conf_logit), label [B] int64 =
+        logit.max(1)[1]) - engine-owned device tensors, overwritten by the next call; `branched_loss_parts` holds (loss, loss_ce, loss_conf).  No answerable
+        row gives a NaN loss_ce and finite gradients, as the reference's statements do."""
+        if not self.conf_branch:
+            raise RuntimeError("branched_loss_backward: this engine has no confidence branch (Engine(conf_branch=True))")
+        na = self.cfg.num_answers
+        t = target_with_uq
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.dim() != 2 or t.stride(1) != 1 or t.device != self.device:
+            raise ValueError("target_with_uq must be a 2-D f32 tensor with unit inner stride on %s" % self.device)
+        if self.shape is None or tuple(t.shape) != (self.shape[0], na + 1):
+            raise ValueError("target_with_uq must be [B, num_answers + 1] = [%s, %d] (the UQ column last); got %s" % (self.shape[0] if self.shape else "?", na + 1, tuple(t.shape)))
+        B = t.shape[0]
+        io = self._io
+        if "br_conf" not in io:
+            io["br_loss3"] = torch.zeros(3, dtype=torch.float32, device=self.device)
+            io["br_conf"] = torch.empty(B, dtype=torch.float32, device=self.device)
+            io["br_label"] = torch.empty(B, dtype=torch.int64, device=self.device)
+        if self._pending_clip is not None:
+            self.flush_deferred_clip() if accumulate else self.drop_deferred_clip()
+        check(self.lib.rgqa_engine_branched_loss_backward(self.h, ptr(t), t.stride(0), 1 if mce else 0, float(grad_scale), 1 if conf_only else 0,
+                                                          ptr(io["br_loss3"]), ptr(io["br_conf"]), ptr(io["br_label"]), 1 if accumulate else 0, _stream()))
+        self._wev_refs.pop("bwd", None)
+        self._seg_sumsq_valid = self._seg_sumsq is not None
+        return io["br_loss3"][:1], io["br_conf"], io["br_label"]
+
+    @property
+    def branched_loss_parts(self):
+        """[3] device tensor of the last branched_loss_backward: loss, loss_ce, loss_conf (None before the first call)"""
+        return self._io.get("br_loss3")
 
     def backward_pooled(self, dpooled, accumulate=False):
         """dpooled [B, H]: an f32 view with unit inner stride goes to the engine as it is (its row stride is the call's `ld`)."""

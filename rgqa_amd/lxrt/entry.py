@@ -134,6 +134,10 @@ class LXRTEncoder(nn.Module):
         input_ids, segment_ids, input_mask, lengths = self._tokenize(sents, feats[0].device)
         return self.model.forward_with_head(input_ids, segment_ids, input_mask, feats, token_lengths=lengths)
 
+    def forward_branched(self, sents, feats):
+        input_ids, segment_ids, input_mask, lengths = self._tokenize(sents, feats[0].device)
+        return self.model.forward_branched(input_ids, segment_ids, input_mask, feats, token_lengths=lengths)
+
     def save(self, path):
         torch.save(self.model.state_dict(), os.path.join("%s_LXRT.pth" % path))
 

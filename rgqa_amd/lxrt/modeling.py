@@ -214,6 +214,7 @@ class ArenaBinding(object):
         self.engine = None
         self.params = []          # (spec, nn.Parameter)
         self._versions = None
+        self.respect_frozen = False      # the branched model (attach_head(..., conf_fc)): parameters with requires_grad = False keep .grad = None
 
     def bind(self, engine, named_params):
         import weakref
@@ -278,6 +279,16 @@ class ArenaBinding(object):
         gv = getattr(self, "_grad_versions", None)
         return gv is not None and gv == sum(g._version for g in (raw_grad(p) for sp, p in self.params if not sp.dead) if g is not None)
 
+    def _skips(self, p):
+        """a frozen parameter of the branched model (tasks/gqa_branched.py:80-83): it never gets a gradient view"""
+        return self.respect_frozen and not p.requires_grad
+
+    def conf_only(self):
+        """the reference's --freeze_vqa_branch state: every parameter outside conf_fc frozen, every conf_fc parameter trained"""
+        if not self.respect_frozen:
+            return False
+        return all(p.requires_grad == sp.name.startswith("conf") for sp, p in self.params)
+
     def _views(self):
         """the gradient-arena view of every live parameter, made once per gradient arena: re-attaching them after the trainer's
         zero_grad() (which sets every .grad to None) is then 439 attribute stores instead of 439 x (slice + view) tensor constructions
@@ -297,7 +308,7 @@ class ArenaBinding(object):
         none = views = 0
         live = 0
         for (sp, p), v in zip(self.params, gv):
-            if v is None:
+            if v is None or self._skips(p):
                 continue
             live += 1
             g = raw_grad(p)
@@ -315,7 +326,7 @@ class ArenaBinding(object):
         gv = self._views()
         ver = 0
         for (sp, p), v in zip(self.params, gv):
-            if v is None:
+            if v is None or self._skips(p):
                 continue
             g = raw_grad(p)
             if g is None:
@@ -443,6 +454,68 @@ class _EngineFunction(torch.autograd.Function):
         return (None, None, dfeats.view(ctx.in_shapes[0]) if want_f else None, dboxes.view(ctx.in_shapes[1]) if want_b else None, None, None, None, None)
 
 
+class _BranchedFunction(torch.autograd.Function):
+    """Autograd boundary of the branched model (tasks/gqa_model_branched.py:47-51): ONE engine forward gives the logits and the conf logits, and whatever
+    combination of dlogits / dconf arrives is ONE engine backward (rgqa_engine_backward2) - the conf head's share joins d(pooler pre-tanh) inside the
+    engine.  With everything outside conf_fc frozen (--freeze_vqa_branch) the pass is the engine's conf_only one: no answer-head or encoder backward."""
+
+    @staticmethod
+    def forward(ctx, anchor, owner, feats, boxes, ids, mask, seg):
+        lg, _ = owner._engine_forward(feats, boxes, ids, mask, seg, train=owner.training)
+        ctx.set_materialize_grads(False)
+        ctx.owner = owner
+        ctx.in_shapes = (tuple(feats.shape), tuple(boxes.shape))
+        ctx.gen = owner._fwd_counter
+        return lg.clone(), owner._binding.engine.conf_logit.clone().unsqueeze(1)
+
+    @staticmethod
+    def backward(ctx, dlogits, dconf):
+        owner = ctx.owner
+        if ctx.gen != owner._fwd_counter:
+            raise RuntimeError("rgqa: backward() after a newer forward of the same module; the engine keeps the activations of "
+                               "the last forward only")
+        b = owner._binding
+        state = b.grads_state()
+        if state == "foreign":
+            raise RuntimeError("rgqa: parameter .grad tensors were replaced by foreign tensors; use zero_grad() / set_to_none")
+        acc = state == "views"
+        e = b.engine
+        if getattr(e, "_pending_clip", None) is not None:
+            if acc:
+                e.flush_deferred_clip()
+            else:
+                e.drop_deferred_clip()
+        conf_only = b.conf_only()
+        want_f, want_b = ctx.needs_input_grad[2], ctx.needs_input_grad[3]
+        if conf_only and (want_f or want_b):
+            raise RuntimeError("rgqa: input gradients are not available while everything outside conf_fc is frozen (no encoder backward is run)")
+        dfeats = torch.empty(ctx.in_shapes[0][0] * ctx.in_shapes[0][1], ctx.in_shapes[0][2], dtype=torch.float32, device=e.device) if want_f else None
+        dboxes = torch.empty(ctx.in_shapes[1][0] * ctx.in_shapes[1][1], ctx.in_shapes[1][2], dtype=torch.float32, device=e.device) if want_b else None
+        if want_f or want_b:
+            e.set_input_grads(dfeats, dboxes)
+        # data parallelism: as _EngineFunction - conf_fc lies in the gradient arena, so the exchange covers it without further code
+        rank, world = _dp_rank_world()
+        dp = _dp_exchanging(world) and owner.training and _SCORING_DEPTH == 0
+        if dp:
+            if acc:
+                raise RuntimeError("rgqa: gradient accumulation over several backward() calls is not supported under data parallelism "
+                                   "(the exchange would count the earlier contributions again): call zero_grad() before every backward")
+            dlogits = None if dlogits is None else dlogits * (1.0 / world)
+            dconf = None if dconf is None else dconf * (1.0 / world)
+        try:
+            if conf_only:
+                e.backward_conf_only(dconf if dconf is not None else torch.zeros(ctx.in_shapes[0][0], device=e.device), accumulate=acc)
+            elif dlogits is not None or dconf is not None:
+                e.backward(dlogits, accumulate=acc, dconf=dconf)
+        finally:
+            if want_f or want_b:
+                e.set_input_grads(None, None)
+        if dp:
+            owner._dp_exchange().all_reduce()
+        b.attach_grads()
+        return (None, None, dfeats.view(ctx.in_shapes[0]) if want_f else None, dboxes.view(ctx.in_shapes[1]) if want_b else None, None, None, None)
+
+
 class BertPreTrainedModel(nn.Module):
     def __init__(self, config, *inputs, **kwargs):
         super(BertPreTrainedModel, self).__init__()
@@ -475,6 +548,7 @@ class LXRTFeatureExtraction(BertPreTrainedModel):
         self.mode = mode
         self.precision = precision or os.environ.get("RGQA_PRECISION", "bf16")
         self.__dict__["_head"] = None          # not a registered submodule: the head belongs to GQAModel's state_dict
+        self.__dict__["_conf_head"] = None     # ... and conf_fc to GQAModel_branched's
         self._binding = ArenaBinding()
         self._fwd_counter = 0
         self._seed_base = None
@@ -498,13 +572,15 @@ class LXRTFeatureExtraction(BertPreTrainedModel):
                                       inter=c.intermediate_size, max_pos=c.max_position_embeddings, type_vocab=c.type_vocab_size,
                                       l_layers=VISUAL_CONFIG.l_layers, x_layers=VISUAL_CONFIG.x_layers, r_layers=VISUAL_CONFIG.r_layers,
                                       feat_dim=VISUAL_CONFIG.visual_feat_dim, pos_dim=VISUAL_CONFIG.visual_pos_dim,
-                                      num_answers=num_answers, precision=self.precision,
+                                      num_answers=num_answers, precision=self.precision, conf_branch=self.__dict__.get("_conf_head") is not None,
                                       hidden_dropout=c.hidden_dropout_prob, attn_dropout=c.attention_probs_dropout_prob)
 
     def _named_for_binding(self):
         named = {self.TREE_PREFIX + k: v for k, v in self.named_parameters()}
         if self._head is not None:
             named.update({"logit_fc." + k: v for k, v in self._head.named_parameters()})
+            if self._conf_head is not None:
+                named.update({"conf_fc." + k: v for k, v in self._conf_head.named_parameters()})
         else:
             # encoder-only use: the engine still owns an (unused) head; keep its slices as hidden zero parameters
             e = self._binding.engine
@@ -517,10 +593,18 @@ class LXRTFeatureExtraction(BertPreTrainedModel):
     def _rebind(self):
         self._binding.bind(self._binding.engine, self._named_for_binding())
 
-    def attach_head(self, logit_fc):
-        """Fuses a GQA answer head (nn.Sequential(Linear, GeLU, LayerNorm, Linear), tasks/gqa_model.py:22-27) into the engine."""
+    def attach_head(self, logit_fc, conf_fc=None):
+        """Fuses a GQA answer head (nn.Sequential(Linear, GeLU, LayerNorm, Linear), tasks/gqa_model.py:22-27) into the engine; conf_fc: also the
+        confidence branch of the branched model (the same Sequential with one output, tasks/gqa_model_branched.py:28-33)."""
         lin0, lin3 = logit_fc[0], logit_fc[3]
         H = self.config.hidden_size
+        if conf_fc is not None:
+            c0, c3 = conf_fc[0], conf_fc[3]
+            if not (isinstance(c0, nn.Linear) and isinstance(c3, nn.Linear) and isinstance(conf_fc[2], nn.LayerNorm) and c0.in_features == H
+                    and c0.out_features == 2 * H and c3.in_features == 2 * H and c3.out_features == 1):
+                raise ValueError("attach_head expects conf_fc = Linear(H,2H) -> GeLU -> LayerNorm(2H) -> Linear(2H,1)")
+        self.__dict__["_conf_head"] = conf_fc
+        self._binding.respect_frozen = conf_fc is not None
         if not (isinstance(lin0, nn.Linear) and isinstance(lin3, nn.Linear) and isinstance(logit_fc[2], nn.LayerNorm)
                 and lin0.in_features == H and lin0.out_features == 2 * H and lin3.in_features == 2 * H):
             raise ValueError("attach_head expects Linear(H,2H) -> GeLU -> LayerNorm(2H) -> Linear(2H,NA)")
@@ -611,6 +695,25 @@ class LXRTFeatureExtraction(BertPreTrainedModel):
         feats, boxes = visual_feats
         _, pooled = self._run(feats, boxes, input_ids, attention_mask, token_type_ids, want_logits=False, lengths=token_lengths)
         return pooled
+
+    def forward_branched(self, input_ids, token_type_ids, attention_mask, visual_feats, token_lengths=None):
+        """Encoder + fused answer head + fused confidence branch -> (logits [B, NA], conf [B, 1]) from one engine forward."""
+        if self._head is None or self._conf_head is None:
+            raise RuntimeError("no confidence branch attached (attach_head(logit_fc, conf_fc))")
+        feats, boxes = visual_feats
+        if token_lengths is not None:
+            self.__dict__["_pending_lengths"] = token_lengths
+        feats, boxes = feats.contiguous().float(), boxes.contiguous().float()
+        if feats.device.type != "cuda":
+            raise RuntimeError("rgqa_amd: inputs must be on the MI355X (device 'cuda'); there is no CPU path")
+        ids, mask = input_ids.contiguous().long(), attention_mask.contiguous().long()
+        seg = None if token_type_ids is None else token_type_ids.contiguous().long()
+        if torch.is_grad_enabled():
+            if self._anchor is None or self._anchor.device != feats.device:
+                self.__dict__["_anchor"] = torch.zeros(1, device=feats.device, requires_grad=True)
+            return _BranchedFunction.apply(self._anchor, self, feats, boxes, ids, mask, seg)
+        lg, _ = self._engine_forward(feats, boxes, ids, mask, seg, train=self.training)
+        return lg.clone(), self._binding.engine.conf_logit.clone().unsqueeze(1)
 
     def forward_with_head(self, input_ids, token_type_ids, attention_mask, visual_feats, token_lengths=None):
         """Encoder + fused answer head -> (logits, pooled)."""

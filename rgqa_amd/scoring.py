@@ -34,6 +34,12 @@ forward of the concatenated [positive ; negative] batch (the weight parameters t
     loss_pos = mean(bce(logit_pos, target_pos)) * NA;  loss_neg = (weights @ bce(logit_neg, target_neg)).sum() / Bn           :196-200   resample_loss_rows
     loss = loss_pos + loss_neg;  loss_w = -loss_neg, under autograd for the model, closed form for the weight parameters      :202-203   resample_finetune_loss
 
+and the loss head and the scorer of the confidence-branch model (tasks/gqa_branched.py, GQAModel_branched; csrc/branched_loss.hip):
+
+    id_inds = target[:, -1] == 0; loss_ce over logit[id_inds] (BCE x NA, or --mce_loss) + binary_cross_entropy(sigmoid(conf), id_inds)     :126-142   branched_loss_rows
+    the same under autograd over (logit, conf), for `loss.backward()` through GQAModel_branched: ONE engine backward                      :126-143   branched_finetune_loss
+    score1, label = sigmoid(logit).max(1); score2 = sigmoid(conf); score = score2, or score1 * score2 with --mix_branched_score            :206-214   branched_scores
+
 There is no CPU fallback: without the HIP library this raises."""
 import collections
 import ctypes as C
@@ -50,6 +56,7 @@ MahaRows = collections.namedtuple("MahaRows", "score label y all_scores pooled")
 MahaScores = collections.namedtuple("MahaScores", "score label pooled feats_pt boxes_pt")
 EnergyLoss = collections.namedtuple("EnergyLoss", "loss base reg dlogits energy label")
 ResampleLoss = collections.namedtuple("ResampleLoss", "loss loss_pos loss_neg dlogits row_loss")
+BranchedLoss = collections.namedtuple("BranchedLoss", "loss loss_ce loss_conf dlogits dconf conf label score1")
 
 
 def score_rows(logits, temperature=1.0, k=0):
@@ -476,3 +483,74 @@ def resample_finetune_loss(logit, target_with_uq, n_pos, rw, wids):
     loss, loss_w, row_loss = _ResampleFinetuneLoss.apply(logit, target_with_uq, n_pos, weights)
     rw.row_loss = row_loss
     return loss, loss_w
+
+
+# ------------------------------------------------------------------------------------------------ confidence branch (tasks/gqa_branched.py)
+def _branched_args(name, logits, conf, target_with_uq):
+    if not (isinstance(logits, torch.Tensor) and logits.is_cuda and logits.dtype == torch.float32 and logits.dim() == 2):
+        raise ValueError("%s: logits must be a 2-D float32 CUDA tensor" % name)
+    B, NA = logits.shape
+    if not (isinstance(conf, torch.Tensor) and conf.dtype == torch.float32 and conf.device == logits.device and conf.numel() == B and conf.dim() in (1, 2)):
+        raise ValueError("%s: conf must be a float32 [B] or [B, 1] = [%d] tensor on the logits' device" % (name, B))
+    t = target_with_uq
+    if not (isinstance(t, torch.Tensor) and t.dtype == torch.float32 and t.dim() == 2 and t.device == logits.device and tuple(t.shape) == (B, NA + 1)):
+        raise ValueError("%s: target_with_uq must be a float32 [B, NA + 1] = [%d, %d] tensor on the logits' device, the UQ column last" % (name, B, NA + 1))
+    return (logits if logits.stride(1) == 1 else logits.contiguous()), conf.reshape(-1).contiguous(), (t if t.stride(1) == 1 else t.contiguous())
+
+
+def branched_loss_rows(logits, conf, target_with_uq, mce_loss=False, grad_scale=1.0):
+    """gqa_branched.py:126-142, :147 and :209 on given logits and conf logits, one fused pass (`rgqa_op_branched_loss`).  logits: f32 CUDA [B, NA], any row
+    stride; conf: f32 [B] or [B, 1] conf LOGITS (before the sigmoid); target_with_uq: f32 [B, NA + 1], the last column the UQ flag (non-zero =
+    unanswerable), read in place.  Returns BranchedLoss(loss, loss_ce, loss_conf: 0-dim views of one [3] tensor; dlogits [B, NA] and dconf [B] = d loss / d
+    logits, d loss / d conf logits, times grad_scale; conf [B] = sigmoid(conf); label [B] int64 = logit.max(1)[1]; score1 [B] = sigmoid(logit).max(1)[0]).
+    No answerable row gives loss = loss_ce = NaN and finite gradients, as the reference's statements do.  loss_conf is formed in the stable form
+    max(c, 0) - c y + log1p(exp(-|c|)) (each term capped at 100): it departs from torch's f32 statements where their sigmoid saturates (|c| >~ 17)."""
+    z, c, t = _branched_args("branched_loss_rows", logits, conf, target_with_uq)
+    lib = _lib.load()
+    B, NA = z.shape
+    dev = z.device
+    n = C.c_size_t()
+    _lib.check(lib.rgqa_op_branched_loss_scratch_floats(B, C.byref(n)))
+    scratch = torch.empty(n.value, dtype=torch.float32, device=dev)
+    loss = torch.empty(3, dtype=torch.float32, device=dev)
+    dl = torch.empty(B, NA, dtype=torch.float32, device=dev)
+    dc, cf, s1 = (torch.empty(B, dtype=torch.float32, device=dev) for _ in range(3))
+    lab = torch.empty(B, dtype=torch.int64, device=dev)
+    p = _lib.ptr
+    _lib.check(lib.rgqa_op_branched_loss(p(z), z.stride(0), p(c), p(t), t.stride(0), B, NA, NA, 1 if mce_loss else 0, float(grad_scale), p(loss), p(dl), dl.stride(0),
+                                         p(dc), p(cf), p(lab), p(s1), p(scratch), _stream(dev)))
+    return BranchedLoss(loss[0], loss[1], loss[2], dl, dc, cf, lab, s1)
+
+
+class _BranchedFinetuneLoss(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, logit, conf, target_with_uq, mce_loss):
+        r = branched_loss_rows(logit.detach(), conf.detach(), target_with_uq, mce_loss)
+        ctx.save_for_backward(r.dlogits, r.dconf)
+        ctx.conf_shape = tuple(conf.shape)
+        ctx.mark_non_differentiable(r.loss_ce, r.loss_conf, r.conf, r.label)
+        return r.loss.clone(), r.loss_ce, r.loss_conf, r.conf, r.label
+
+    @staticmethod
+    def backward(ctx, grad_loss, *unused):
+        dl, dc = ctx.saved_tensors
+        return grad_loss * dl, (grad_loss * dc).view(ctx.conf_shape), None, None
+
+
+def branched_finetune_loss(logit, conf, target_with_uq, mce_loss=False):
+    """What a trainer puts in place of gqa_branched.py:126-142 and :147: `loss, loss_ce, loss_conf, conf, label = branched_finetune_loss(*model(feats, boxes,
+    sent), target, mce_loss=args.mce_loss)` with `target` as the loader gives it (UQ column last); `loss.backward()`, `clip_grad_norm_` and `BertAdam.step()`
+    stay as they are.  logit [B, NA], conf [B, 1]: the outputs of GQAModel_branched.  Returns (loss 0-dim, loss_ce, loss_conf, sigmoid(conf) [B], label [B]):
+    the forward runs the fused operator once and keeps dlogits and dconf, the backward hands both to the model's autograd boundary - ONE engine backward."""
+    _branched_args("branched_finetune_loss", logit, conf, target_with_uq)
+    return _BranchedFinetuneLoss.apply(logit, conf, target_with_uq, bool(mce_loss))
+
+
+def branched_scores(model, feats, boxes, sent, mix=False):
+    """One batch of the branched model's OOD scorer (gqa_branched.py:206-214) under no_grad: score = sigmoid(conf), or with mix=True (--mix_branched_score)
+    sigmoid(conf) * max sigmoid(logit); label = sigmoid(logit).max(1)[1].  Returns (score [B], label [B] int64)."""
+    with torch.no_grad():
+        logit, conf = model(feats, boxes, sent)
+    s = score_rows(logit)
+    score2 = torch.sigmoid(conf).reshape(-1)
+    return (s.max_score * score2 if mix else score2), s.label

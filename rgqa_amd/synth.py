@@ -47,7 +47,7 @@ def fill_value(name, shape):
     """
     leaf = name.rsplit(".", 1)[-1]
     parent = name.rsplit(".", 2)[-2] if name.count(".") >= 1 else ""
-    is_ln = "LayerNorm" in parent or "layer_norm" in parent or name.startswith("logit_fc.2.")
+    is_ln = "LayerNorm" in parent or "layer_norm" in parent or name.startswith("logit_fc.2.") or name.startswith("conf_fc.2.")
     if is_ln:
         if leaf == "weight":
             return 1.0 + uniform(name, shape, -0.1, 0.1)
@@ -124,6 +124,16 @@ def small_batch(T):
     b["input_ids"][1, 0] = 2
     b["input_mask"] = (b["input_ids"] != 0).astype(np.int64)
     return b
+
+
+# The confidence-branch fixture (tests/golden/g15_branched.npz, tools/gen_g15_branched.py): small_batch(8) under a target that carries the UQ column, row 1
+# unanswerable (tasks/gqa_branched.py:126-127), two soft entries in row 0 so that the BCE and the cross-entropy forms differ
+def branched_target():
+    t = np.zeros((3, SMALL["num_answers"] + 1), dtype=np.float32)
+    t[0, 3], t[0, 7] = 1.0, 0.5
+    t[1, -1] = 1.0
+    t[2, 9] = 1.0
+    return t
 
 
 def full_batch(T):
