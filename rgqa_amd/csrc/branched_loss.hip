@@ -10,7 +10,7 @@
 // Laid out like energy_loss.hip: the rows meet only in n_id, which the B flags alone fix - every workgroup counts it itself and finishes its row in ONE
 // launch; a second one-workgroup launch folds the row shares in a fixed order.  No float atomics: results repeat bit for bit.
 //
-// Arithmetic.  The element formulas of the BCE form are loss.hip's (kernels.h bce_term / bce_sigmoid); row sums are carried in f64 and travel to the fold
+// Arithmetic.  The element formulas of the BCE form are loss.hip's (rowops.h bce_term / bce_sigmoid); row sums are carried in f64 and travel to the fold
 // as (hi, lo) float pairs, as in energy_loss.hip.  The confidence term is one number per row and is formed in f64 in the stable (softplus) form
 //   BCE(sigmoid(c), y) = max(c, 0) - c y + log1p(exp(-|c|)),   capped at 100 as torch's log clamp at -100 caps it.
 // torch's own f32 path saturates sigmoid(c) to exactly 1 (c >~ 17) or to a denormal / 0 (c <~ -88) first and then clamps the log: its loss term of a
@@ -31,44 +31,6 @@ struct BranchedLossArgs {
     int vz, vt, vd;                 // 16-byte accesses allowed for z / t / dz
 };
 
-__device__ __forceinline__ double bl_wave_sum_d(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-__device__ __forceinline__ int bl_wave_sum_i(int v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-// (value, index): the larger value wins, among equal values the lower index - the first maximum, whatever the order the candidates meet in
-__device__ __forceinline__ void bl_first_max(float& v, int& i, float ov, int oi) {
-    if (ov > v || (ov == v && oi < i)) { v = ov; i = oi; }
-}
-__device__ __forceinline__ void bl_wave_first_max(float& v, int& i) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const float ov = __shfl_xor(v, o, 64);
-        const int oi = __shfl_xor(i, o, 64);
-        bl_first_max(v, i, ov, oi);
-    }
-}
-// columns n .. n + 3 of a row (n % 4 == 0); columns >= lim read as `fill` and are never touched in memory
-__device__ __forceinline__ void bl_load4(const float* row, int n, int lim, int vec, float fill, float v[4]) {
-    if (vec && n + 3 < lim) { load4(row + n, v); return; }
-#pragma unroll
-    for (int j = 0; j < 4; ++j) v[j] = n + j < lim ? row[n + j] : fill;
-}
-__device__ __forceinline__ void bl_store4(float* row, int n, int lim, int vec, const float v[4]) {
-    if (vec && n + 3 < lim) { store4(row + n, v); return; }
-#pragma unroll
-    for (int j = 0; j < 4; ++j) if (n + j < lim) row[n + j] = v[j];
-}
-__device__ __forceinline__ void bl_split_store(float* p, double v) {
-    const float hi = (float)v;
-    p[0] = hi; p[1] = (float)(v - (double)hi);
-}
-
 __global__ __launch_bounds__(BL_T) void branched_loss_kernel(BranchedLossArgs a) {
     __shared__ double sd[2][4];
     __shared__ float sv[2][4];
@@ -80,7 +42,7 @@ __global__ __launch_bounds__(BL_T) void branched_loss_kernel(BranchedLossArgs a)
     // ---- the count of the unanswerable rows (every workgroup for itself: B flags)
     int n_out = 0;
     for (int r = tid; r < a.B; r += BL_T) n_out += a.t[(size_t)r * a.ldt + a.NA] != 0.f ? 1 : 0;
-    n_out = bl_wave_sum_i(n_out);
+    n_out = wave_sum_i(n_out);
     if (lane == 0) si[0][w] = n_out;
     const bool uq = t[a.NA] != 0.f;
 
@@ -90,8 +52,8 @@ __global__ __launch_bounds__(BL_T) void branched_loss_kernel(BranchedLossArgs a)
     float tv = -INFINITY; int ti = 0x7fffffff;
     for (int n = 4 * tid; n < a.NA; n += 4 * BL_T) {
         float x[4], y[4];
-        bl_load4(z, n, a.NA, a.vz, 0.f, x);
-        bl_load4(t, n, a.NA, a.vt, 0.f, y);
+        row_load4(z, n, a.NA, a.vz, 0.f, x);
+        row_load4(t, n, a.NA, a.vt, 0.f, y);
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             if (n + j < a.NA) {
@@ -101,14 +63,14 @@ __global__ __launch_bounds__(BL_T) void branched_loss_kernel(BranchedLossArgs a)
             }
         }
     }
-    acc = bl_wave_sum_d(acc);
-    bl_wave_first_max(zm, zi);
-    bl_wave_first_max(tv, ti);
+    acc = wave_sum_d(acc);
+    wave_first_max(zm, zi);
+    wave_first_max(tv, ti);
     if (lane == 0) { sd[0][w] = acc; sv[0][w] = zm; si[1][w] = zi; sv[1][w] = tv; si[2][w] = ti; }
     __syncthreads();
     zm = sv[0][0]; zi = si[1][0]; tv = sv[1][0]; ti = si[2][0];
 #pragma unroll
-    for (int k = 1; k < 4; ++k) { bl_first_max(zm, zi, sv[0][k], si[1][k]); bl_first_max(tv, ti, sv[1][k], si[2][k]); }
+    for (int k = 1; k < 4; ++k) { first_max(zm, zi, sv[0][k], si[1][k]); first_max(tv, ti, sv[1][k], si[2][k]); }
     n_out = (si[0][0] + si[0][1]) + (si[0][2] + si[0][3]);
     const int n_id = a.B - n_out;
     double share = (sd[0][0] + sd[0][1]) + (sd[0][2] + sd[0][3]);
@@ -119,11 +81,11 @@ __global__ __launch_bounds__(BL_T) void branched_loss_kernel(BranchedLossArgs a)
         double se = 0.0;
         for (int n = 4 * tid; n < a.NA; n += 4 * BL_T) {
             float x[4];
-            bl_load4(z, n, a.NA, a.vz, 0.f, x);
+            row_load4(z, n, a.NA, a.vz, 0.f, x);
 #pragma unroll
             for (int j = 0; j < 4; ++j) if (n + j < a.NA) se += (double)expf(x[j] - zm);
         }
-        se = bl_wave_sum_d(se);
+        se = wave_sum_d(se);
         if (lane == 0) sd[1][w] = se;
         __syncthreads();
         se = (sd[1][0] + sd[1][1]) + (sd[1][2] + sd[1][3]);
@@ -142,8 +104,8 @@ __global__ __launch_bounds__(BL_T) void branched_loss_kernel(BranchedLossArgs a)
         if (a.rows) {
             const double cd = (double)c;
             const double term = fmin(fmax(cd, 0.0) - cd * (double)idf + log1p(exp(-fabs(cd))), 100.0);
-            bl_split_store(a.rows + 4 * (size_t)b, uq ? 0.0 : share);
-            bl_split_store(a.rows + 4 * (size_t)b + 2, term);
+            split_store(a.rows + 4 * (size_t)b, uq ? 0.0 : share);
+            split_store(a.rows + 4 * (size_t)b + 2, term);
         }
     }
     if (a.dz == nullptr) return;
@@ -153,8 +115,8 @@ __global__ __launch_bounds__(BL_T) void branched_loss_kernel(BranchedLossArgs a)
     for (int n = 4 * tid; n < a.NAp; n += 4 * BL_T) {
         float x[4], y[4], g[4];
         if (!uq) {
-            bl_load4(z, n, a.NA, a.vz, 0.f, x);
-            if (!a.mce) bl_load4(t, n, a.NA, a.vt, 0.f, y);
+            row_load4(z, n, a.NA, a.vz, 0.f, x);
+            if (!a.mce) row_load4(t, n, a.NA, a.vt, 0.f, y);
         }
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
@@ -165,7 +127,7 @@ __global__ __launch_bounds__(BL_T) void branched_loss_kernel(BranchedLossArgs a)
             }
             g[j] = v;
         }
-        bl_store4(d, n, a.NAp, a.vd, g);
+        row_store4(d, n, a.NAp, a.vd, g);
     }
 }
 
@@ -183,7 +145,7 @@ __global__ __launch_bounds__(BL_T) void branched_loss_fold_kernel(const float* _
         if (t[(size_t)b * ldt + NA] != 0.f) ++n_out; else ce += (double)r[0] + (double)r[1];
         cf += (double)r[2] + (double)r[3];
     }
-    ce = bl_wave_sum_d(ce); cf = bl_wave_sum_d(cf); n_out = bl_wave_sum_i(n_out);
+    ce = wave_sum_d(ce); cf = wave_sum_d(cf); n_out = wave_sum_i(n_out);
     if (lane == 0) { sd[0][w] = ce; sd[1][w] = cf; si[w] = n_out; }
     __syncthreads();
     if (tid != 0) return;
@@ -197,8 +159,6 @@ __global__ __launch_bounds__(BL_T) void branched_loss_fold_kernel(const float* _
 
 size_t k_branched_loss_scratch_floats(int B) { return B > 0 ? 4 * (size_t)B : 0; }
 
-static inline int bl_vec_ok(const float* p, int ld) { return p != nullptr && (reinterpret_cast<uintptr_t>(p) & 15) == 0 && (ld & 3) == 0; }
-
 int k_branched_loss(const float* logits, int ld, const float* conf_logit, const float* target_with_uq, int ldt, int B, int NA, int NAp, int mce, float grad_scale,
                     float* loss3, float* dlogits, int ldd, float* dconf, float* conf, int64_t* label, float* score1, float* scratch, hipStream_t s) {
     RGQA_REQUIRE(logits != nullptr && conf_logit != nullptr && target_with_uq != nullptr, "branched_loss: null logits / conf_logit / target pointer");
@@ -210,7 +170,7 @@ int k_branched_loss(const float* logits, int ld, const float* conf_logit, const 
     a.z = logits; a.ld = ld; a.c = conf_logit; a.t = target_with_uq; a.ldt = ldt;
     a.B = B; a.NA = NA; a.NAp = NAp; a.mce = mce ? 1 : 0; a.gscale = grad_scale;
     a.dz = dlogits; a.ldd = ldd; a.dconf = dconf; a.conf = conf; a.label = label; a.score1 = score1; a.rows = loss3 ? scratch : nullptr;
-    a.vz = bl_vec_ok(logits, ld); a.vt = bl_vec_ok(target_with_uq, ldt); a.vd = bl_vec_ok(dlogits, ldd);
+    a.vz = vec16_ok(logits, ld); a.vt = vec16_ok(target_with_uq, ldt); a.vd = vec16_ok(dlogits, ldd);
     hipLaunchKernelGGL(branched_loss_kernel, dim3(B), dim3(BL_T), 0, s, a);
     RGQA_LAUNCH_CHECK("branched_loss_kernel");
     if (loss3) {

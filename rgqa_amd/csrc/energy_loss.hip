@@ -10,7 +10,7 @@
 // (the 7-KiB row is re-read from cache for the gradient sweep); a second one-workgroup launch folds the row shares of the loss in a fixed order.
 // No float atomics anywhere: results repeat bit for bit.
 //
-// Arithmetic.  The element formulas of the BCE form are loss.hip's (kernels.h bce_term / bce_sigmoid): with c_b an exact zero - weight 0, or a row
+// Arithmetic.  The element formulas of the BCE form are loss.hip's (rowops.h bce_term / bce_sigmoid): with c_b an exact zero - weight 0, or a row
 // whose hinge is inactive - a row of dlogits has the bits bce_kernel gives.  The softplus is score.hip's naive one, as the reference writes it (+inf
 // above logit 88.7 like torch's; nothing is promised there).  Row sums (loss share, energy, softmax denominator) are carried in f64 and the row shares
 // travel to the fold as (hi, lo) float pairs: 1842 f32 terms summed in f32 would lose 3-4 bits of a loss that a trainer compares between runs to 7
@@ -18,7 +18,8 @@
 //
 // Element -> thread mapping.  Thread t owns the column quads 4 (t + 256 i) .. + 3.  A quad is ONE 16-byte access where base and pitch of the operand
 // allow (the engines' logits and dlogits: pitch NAp, a multiple of 64) and four 4-byte accesses where they do not (a target of NA + 1 columns: rows
-// start on odd words); the mapping - and with it every sum's order - is the same in both forms, so a result does not depend on the operands' alignment.
+// start on odd words); the mapping - and with it every sum's order - is the same in both forms, so a result does not depend on the operands' alignment
+// (rowops.h row_load4 / row_store4, with the fixed-order reductions).
 #include "kernels.h"
 
 #define EL_T 256
@@ -34,44 +35,6 @@ struct EnergyLossArgs {
     float* rows;                    // [B][4]: loss share hi, lo | hinge^2 hi, lo  (null: no loss asked for)
     int vz, vt, vd;                 // 16-byte accesses allowed for z / t / dz
 };
-
-__device__ __forceinline__ double wave_sum_d(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-__device__ __forceinline__ int wave_sum_i(int v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-// (value, index): the larger value wins, among equal values the lower index - the first maximum, whatever the order the candidates meet in
-__device__ __forceinline__ void first_max(float& v, int& i, float ov, int oi) {
-    if (ov > v || (ov == v && oi < i)) { v = ov; i = oi; }
-}
-__device__ __forceinline__ void wave_first_max(float& v, int& i) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const float ov = __shfl_xor(v, o, 64);
-        const int oi = __shfl_xor(i, o, 64);
-        first_max(v, i, ov, oi);
-    }
-}
-// columns n .. n + 3 of a row (n % 4 == 0); columns >= lim read as `fill` and are never touched in memory
-__device__ __forceinline__ void el_load4(const float* row, int n, int lim, int vec, float fill, float v[4]) {
-    if (vec && n + 3 < lim) { load4(row + n, v); return; }
-#pragma unroll
-    for (int j = 0; j < 4; ++j) v[j] = n + j < lim ? row[n + j] : fill;
-}
-__device__ __forceinline__ void el_store4(float* row, int n, int lim, int vec, const float v[4]) {
-    if (vec && n + 3 < lim) { store4(row + n, v); return; }
-#pragma unroll
-    for (int j = 0; j < 4; ++j) if (n + j < lim) row[n + j] = v[j];
-}
-__device__ __forceinline__ void split_store(float* p, double v) {
-    const float hi = (float)v;
-    p[0] = hi; p[1] = (float)(v - (double)hi);        // (inf / NaN: lo = NaN, and hi + lo is NaN / inf again in the fold - nothing is promised there)
-}
 
 __global__ __launch_bounds__(EL_T) void energy_loss_kernel(EnergyLossArgs a) {
     __shared__ double sd[3][4];
@@ -96,8 +59,8 @@ __global__ __launch_bounds__(EL_T) void energy_loss_kernel(EnergyLossArgs a) {
         double acc = 0.0, en = 0.0;
         for (int n = 4 * tid; n < a.NA; n += 4 * EL_T) {
             float x[4], y[4];
-            el_load4(z, n, a.NA, a.vz, 0.f, x);
-            el_load4(t, n, a.NA, a.vt, 0.f, y);
+            row_load4(z, n, a.NA, a.vz, 0.f, x);
+            row_load4(t, n, a.NA, a.vt, 0.f, y);
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 if (n + j < a.NA) {
@@ -118,8 +81,8 @@ __global__ __launch_bounds__(EL_T) void energy_loss_kernel(EnergyLossArgs a) {
         float zm = -INFINITY, tv = -INFINITY; int ti = 0x7fffffff;
         for (int n = 4 * tid; n < a.NA; n += 4 * EL_T) {
             float x[4], y[4];
-            el_load4(z, n, a.NA, a.vz, 0.f, x);
-            el_load4(t, n, a.NA, a.vt, 0.f, y);
+            row_load4(z, n, a.NA, a.vz, 0.f, x);
+            row_load4(t, n, a.NA, a.vt, 0.f, y);
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 if (n + j < a.NA) {
@@ -143,7 +106,7 @@ __global__ __launch_bounds__(EL_T) void energy_loss_kernel(EnergyLossArgs a) {
         double se = 0.0;
         for (int n = 4 * tid; n < a.NA; n += 4 * EL_T) {
             float x[4];
-            el_load4(z, n, a.NA, a.vz, 0.f, x);
+            row_load4(z, n, a.NA, a.vz, 0.f, x);
 #pragma unroll
             for (int j = 0; j < 4; ++j) if (n + j < a.NA) se += (double)expf(x[j] - zmax);
         }
@@ -174,8 +137,8 @@ __global__ __launch_bounds__(EL_T) void energy_loss_kernel(EnergyLossArgs a) {
     const float inv_b = 1.0f / (float)a.B, ce_scale = (float)a.NA * inv_b;
     for (int n = 4 * tid; n < a.NAp; n += 4 * EL_T) {
         float x[4], y[4], g[4];
-        el_load4(z, n, a.NA, a.vz, 0.f, x);
-        if (!a.mce) el_load4(t, n, a.NA, a.vt, 0.f, y);
+        row_load4(z, n, a.NA, a.vz, 0.f, x);
+        if (!a.mce) row_load4(t, n, a.NA, a.vt, 0.f, y);
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             float v = 0.f;
@@ -190,7 +153,7 @@ __global__ __launch_bounds__(EL_T) void energy_loss_kernel(EnergyLossArgs a) {
             }
             g[j] = v;
         }
-        el_store4(d, n, a.NAp, a.vd, g);
+        row_store4(d, n, a.NAp, a.vd, g);
     }
 }
 
@@ -224,8 +187,6 @@ __global__ __launch_bounds__(EL_T) void energy_loss_fold_kernel(const float* __r
 
 size_t k_energy_loss_scratch_floats(int B) { return B > 0 ? 4 * (size_t)B : 0; }
 
-static inline int el_vec_ok(const float* p, int ld) { return p != nullptr && (reinterpret_cast<uintptr_t>(p) & 15) == 0 && (ld & 3) == 0; }
-
 int k_energy_loss(const float* logits, int ld, const float* target, int ldt, const float* ood_flag, int ldf, int B, int NA, int NAp, const EnergyLossCfg& c, float grad_scale,
                   float* loss3, float* dlogits, int ldd, float* energy, int64_t* label, float* scratch, hipStream_t s) {
     RGQA_REQUIRE(logits != nullptr && target != nullptr && ood_flag != nullptr, "energy_loss: null logits / target / flag pointer");
@@ -238,7 +199,7 @@ int k_energy_loss(const float* logits, int ld, const float* target, int ldt, con
     a.B = B; a.NA = NA; a.NAp = NAp; a.mce = c.mce ? 1 : 0;
     a.weight = c.weight; a.m_in = c.m_in; a.m_out = c.m_out; a.gscale = grad_scale;
     a.dz = dlogits; a.ldd = ldd; a.energy = energy; a.label = label; a.rows = loss3 ? scratch : nullptr;
-    a.vz = el_vec_ok(logits, ld); a.vt = el_vec_ok(target, ldt); a.vd = el_vec_ok(dlogits, ldd);
+    a.vz = vec16_ok(logits, ld); a.vt = vec16_ok(target, ldt); a.vd = vec16_ok(dlogits, ldd);
     hipLaunchKernelGGL(energy_loss_kernel, dim3(B), dim3(EL_T), 0, s, a);
     RGQA_LAUNCH_CHECK("energy_loss_kernel");
     if (loss3) {

@@ -182,12 +182,7 @@ int k_visn_combine_bwd(const T* dout, int lddo, const T* zf, int ldz, const floa
 int k_bce_fwd_bwd(const float* logits, int ldl, const float* target, int ldt, float* loss_out, float* dlogits, int lddl, int B, int NA, int NAp, float grad_scale, hipStream_t s,
                   float* row_scratch = nullptr /* B floats: the loss is then folded in a fixed order (no float atomics) */);
 #if defined(__HIPCC__)
-// The element formulas of the BCE head, shared by bce_kernel (loss.hip) and energy_loss_kernel (energy_loss.hip): a row of the energy loss whose
-// regulariser coefficient is an exact zero gets the dlogits bits of bce_kernel.
-__device__ __forceinline__ float bce_term(float x, float y) { return fmaxf(x, 0.f) - x * y + log1pf(__expf(-fabsf(x))); }
-__device__ __forceinline__ float bce_sigmoid(float x) { return 1.f / (1.f + __expf(-x)); }
-// log(1 + exp(x)) as the reference writes it (tasks/gqa_energy.py:135,185): +inf above x = 88.7, as torch's (score.hip, energy_loss.hip)
-__device__ __forceinline__ float softplus_naive(float x) { return logf(1.0f + expf(x)); }
+#include "rowops.h"     // the row primitives and element formulas (bce_term, bce_sigmoid, softplus_naive) of the loss heads
 #endif
 
 // ---- energy_loss.hip: the loss head of the energy fine-tuning (tasks/gqa_energy.py:122-138, :144-145) in one pass per row

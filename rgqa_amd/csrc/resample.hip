@@ -10,7 +10,7 @@
 // The gradient is dense: every theta_j moves every step through m1 and mh.
 //
 // Three calls.  k_resample_weights: the two means over N in f64 - per-thread and per-workgroup partials, folded in a fixed order by one workgroup,
-// which also gathers the Bn batch weights.  k_resample_loss: one workgroup per row, bce_kernel's element formulas (kernels.h), one sweep for the
+// which also gathers the Bn batch weights.  k_resample_loss: one workgroup per row, bce_kernel's element formulas (rowops.h), one sweep for the
 // row's BCE sum (f64) and its dlogits; a one-workgroup launch folds the row shares.  k_resample_step: one workgroup names an OWNER for every index
 // that occurs in wid - its first occurrence, which adds the row losses of all occurrences in batch order - and forms S and the three coefficients
 // of the gradient in f64; the pass over N then gives every workgroup a contiguous 1024-index chunk, the owners inside the chunk drop their sum into an
@@ -25,36 +25,12 @@
 #define RS_CHUNK 1024            // indices per workgroup of the step pass: one quad per thread
 #define RS_MAX_PARTS 1024        // workgroups of the sum pass: at most 4 partials per thread of the fold
 
-__device__ __forceinline__ double rs_wave_sum_d(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
 __device__ __forceinline__ void rs_put_d(float* p, double v) { memcpy(p, &v, 8); }            // p is 4-byte aligned only: two word stores
 __device__ __forceinline__ double rs_get_d(const float* p) { double v; memcpy(&v, p, 8); return v; }
 // torch's softplus (beta 1, threshold 20)
 __device__ __forceinline__ float rs_softplus(float x) { return x > 20.f ? x : log1pf(expf(x)); }
 __device__ __forceinline__ double rs_softplus_d(double x) { return x > 20.0 ? x : log1p(exp(x)); }
 __device__ __forceinline__ float rs_dsoftplus(float x) { return x > 20.f ? 1.f : 1.f / (1.f + expf(-x)); }
-// elements n .. n + 3 (n % 4 == 0); elements >= lim read as `fill` and are never touched in memory
-__device__ __forceinline__ void rs_get4(const float* row, int n, int lim, int vec, float fill, float v[4]) {
-    if (vec && n + 3 < lim) { load4(row + n, v); return; }
-#pragma unroll
-    for (int j = 0; j < 4; ++j) v[j] = n + j < lim ? row[n + j] : fill;
-}
-__device__ __forceinline__ void rs_put4(float* row, int n, int lim, int vec, const float v[4]) {
-    if (vec && n + 3 < lim) { store4(row + n, v); return; }
-#pragma unroll
-    for (int j = 0; j < 4; ++j) if (n + j < lim) row[n + j] = v[j];
-}
-// the four wave sums of a workgroup, added in a fixed order (every thread gets the result)
-__device__ __forceinline__ double rs_block_sum_d(double v, double* sh /* [4] */) {
-    v = rs_wave_sum_d(v);
-    __syncthreads();                                   // (sh may still be read from a previous use)
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return (sh[0] + sh[1]) + (sh[2] + sh[3]);
-}
 
 // ------------------------------------------------------------------------------------------------ weights
 // parts[4 g .. 4 g + 3] = workgroup g's sums of w and sqrt(w) (two doubles as four words).  Thread (g, t) owns the quads 4 ((g + G i) 256 + t).
@@ -65,7 +41,7 @@ __global__ __launch_bounds__(RS_T) void resample_sum_kernel(const float* __restr
     for (size_t q = (size_t)blockIdx.x * RS_T + tid; 4 * q < (size_t)N; q += (size_t)gridDim.x * RS_T) {
         float x[4];
         const int n = (int)(4 * q);
-        rs_get4(theta, n, N, vec, 0.f, x);
+        row_load4(theta, n, N, vec, 0.f, x);
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             if (n + j < N) {
@@ -74,8 +50,8 @@ __global__ __launch_bounds__(RS_T) void resample_sum_kernel(const float* __restr
             }
         }
     }
-    s1 = rs_block_sum_d(s1, sh);
-    sh_ = rs_block_sum_d(sh_, sh);
+    s1 = block_sum_d(s1, sh);
+    sh_ = block_sum_d(sh_, sh);
     if (tid == 0) { rs_put_d(parts + 4 * (size_t)blockIdx.x, s1); rs_put_d(parts + 4 * (size_t)blockIdx.x + 2, sh_); }
 }
 
@@ -86,8 +62,8 @@ __global__ __launch_bounds__(RS_T) void resample_weights_kernel(const float* __r
     const int tid = threadIdx.x;
     double s1 = 0.0, sh_ = 0.0;
     for (int g = tid; g < G; g += RS_T) { s1 += rs_get_d(parts + 4 * (size_t)g); sh_ += rs_get_d(parts + 4 * (size_t)g + 2); }
-    s1 = rs_block_sum_d(s1, sh);
-    sh_ = rs_block_sum_d(sh_, sh);
+    s1 = block_sum_d(s1, sh);
+    sh_ = block_sum_d(sh_, sh);
     const double m1 = s1 / (double)N, mh = sh_ / (double)N;
     if (tid == 0) { stats[0] = m1; stats[1] = mh; }
     const float scale = (float)(mh / m1);
@@ -121,8 +97,8 @@ __global__ __launch_bounds__(RS_T) void resample_loss_kernel(ResampleLossArgs a)
     double acc = 0.0;
     for (int n = 4 * tid; n < a.NAp; n += 4 * RS_T) {
         float x[4], y[4], g[4];
-        rs_get4(z, n, a.NA, a.vz, 0.f, x);
-        rs_get4(t, n, a.NA, a.vt, 0.f, y);
+        row_load4(z, n, a.NA, a.vz, 0.f, x);
+        row_load4(t, n, a.NA, a.vt, 0.f, y);
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             float v = 0.f;
@@ -133,12 +109,12 @@ __global__ __launch_bounds__(RS_T) void resample_loss_kernel(ResampleLossArgs a)
             }
             g[j] = v;
         }
-        if (d) rs_put4(d, n, a.NAp, a.vd, g);            // columns NA .. NAp: exact zeros (they feed K-padded GEMMs)
+        if (d) row_store4(d, n, a.NAp, a.vd, g);         // columns NA .. NAp: exact zeros (they feed K-padded GEMMs)
     }
-    acc = rs_block_sum_d(acc, sh);
+    acc = block_sum_d(acc, sh);
     if (tid == 0) {
         if (!pos && a.row_loss) a.row_loss[b - a.n_pos] = (float)acc;
-        if (a.rows) { const float hi = (float)acc; a.rows[2 * (size_t)b] = hi; a.rows[2 * (size_t)b + 1] = (float)(acc - (double)hi); }
+        if (a.rows) split_store(a.rows + 2 * (size_t)b, acc);
     }
 }
 
@@ -151,8 +127,8 @@ __global__ __launch_bounds__(RS_T) void resample_loss_fold_kernel(const float* _
         const double r = (double)rows[2 * (size_t)b] + (double)rows[2 * (size_t)b + 1];
         if (b < n_pos) sp += r; else sn += (double)weights[b - n_pos] * r;
     }
-    sp = rs_block_sum_d(sp, sh);
-    sn = rs_block_sum_d(sn, sh);
+    sp = block_sum_d(sp, sh);
+    sn = block_sum_d(sn, sh);
     if (tid != 0) return;
     const double lp = sp / (double)n_pos, ln = sn / (double)(B - n_pos);
     loss3[0] = (float)(lp + ln); loss3[1] = (float)lp; loss3[2] = (float)ln;
@@ -178,7 +154,7 @@ __global__ __launch_bounds__(RS_T) void resample_owner_kernel(const float* __res
         own_s[b] = (float)s;
         if (first) term += (double)(float)s * sqrt(rs_softplus_d((double)theta[j]));               // S from the owners' sums: [j, j, j] and [j] give the same S
     }
-    const double S = rs_block_sum_d(term, sh);
+    const double S = block_sum_d(term, sh);
     if (tid != 0) return;
     const double m1 = stats[0], mh = stats[1], n = (double)N, bn = (double)Bn;
     scr[0] = (float)(-S / (2.0 * n * m1 * bn));
@@ -205,8 +181,8 @@ __global__ __launch_bounds__(RS_T) void resample_step_kernel(float* __restrict__
     if (lo + 4 * tid >= (int64_t)N) return;
     const int n = (int)lo + 4 * tid;
     float x[4], m[4], g[4];
-    rs_get4(theta, n, N, vth, 0.f, x);
-    rs_get4(buf, n, N, vbuf, 0.f, m);
+    row_load4(theta, n, N, vth, 0.f, x);
+    row_load4(buf, n, N, vbuf, 0.f, m);
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
         const float rs = 1.0f / sqrtf(rs_softplus(x[j]));
@@ -214,14 +190,13 @@ __global__ __launch_bounds__(RS_T) void resample_step_kernel(float* __restrict__
         m[j] = fmaf(momentum, m[j], g[j]);
         x[j] = fmaf(-lr, m[j], x[j]);
     }
-    rs_put4(theta, n, N, vth, x);
-    rs_put4(buf, n, N, vbuf, m);
-    if (grad_out) rs_put4(grad_out, n, N, vg, g);
+    row_store4(theta, n, N, vth, x);
+    row_store4(buf, n, N, vbuf, m);
+    if (grad_out) row_store4(grad_out, n, N, vg, g);
 }
 
 // ------------------------------------------------------------------------------------------------ host
 static inline int rs_parts(int N) { const int g = (N + 4 * RS_T - 1) / (4 * RS_T); return g < 1 ? 1 : (g > RS_MAX_PARTS ? RS_MAX_PARTS : g); }
-static inline int rs_vec_ok(const float* p, int ld) { return p != nullptr && (reinterpret_cast<uintptr_t>(p) & 15) == 0 && (ld & 3) == 0; }
 
 // what any of the three calls needs (they may share one buffer on one stream): the sum pass's partials | 2 floats per row | coefficients + owners
 size_t k_resample_scratch_floats(int N, int B) {
@@ -235,7 +210,7 @@ int k_resample_weights(const float* theta, int N, const int64_t* wid, int Bn, do
     RGQA_REQUIRE(N > 0 && Bn >= 0 && (Bn == 0 || (wid != nullptr && weights != nullptr)), "resample_weights: bad shape N=%d Bn=%d, or null wid / weights", N, Bn);
     RGQA_REQUIRE((reinterpret_cast<uintptr_t>(stats) & 7) == 0, "resample_weights: stats must be 8-byte aligned");
     const int G = rs_parts(N);
-    hipLaunchKernelGGL(resample_sum_kernel, dim3(G), dim3(RS_T), 0, s, theta, N, rs_vec_ok(theta, 0), scratch);
+    hipLaunchKernelGGL(resample_sum_kernel, dim3(G), dim3(RS_T), 0, s, theta, N, vec16_ok(theta, 0), scratch);
     RGQA_LAUNCH_CHECK("resample_sum_kernel");
     hipLaunchKernelGGL(resample_weights_kernel, dim3(1), dim3(RS_T), 0, s, (const float*)scratch, G, theta, N, wid, Bn, stats, weights);
     RGQA_LAUNCH_CHECK("resample_weights_kernel");
@@ -253,7 +228,7 @@ int k_resample_loss(const float* logits, int ld, const float* target, int ldt, i
     a.z = logits; a.ld = ld; a.t = target; a.ldt = ldt; a.weights = weights;
     a.B = B; a.n_pos = n_pos; a.NA = NA; a.NAp = NAp; a.gscale = grad_scale;
     a.dz = dlogits; a.ldd = ldd; a.row_loss = row_loss; a.rows = loss3 ? scratch : nullptr;
-    a.vz = rs_vec_ok(logits, ld); a.vt = rs_vec_ok(target, ldt); a.vd = rs_vec_ok(dlogits, ldd);
+    a.vz = vec16_ok(logits, ld); a.vt = vec16_ok(target, ldt); a.vd = vec16_ok(dlogits, ldd);
     hipLaunchKernelGGL(resample_loss_kernel, dim3(B), dim3(RS_T), 0, s, a);
     RGQA_LAUNCH_CHECK("resample_loss_kernel");
     if (loss3) {
@@ -271,8 +246,8 @@ int k_resample_step(float* theta, float* buf, int N, const int64_t* wid, const f
     hipLaunchKernelGGL(resample_owner_kernel, dim3(1), dim3(RS_T), 0, s, (const float*)theta, N, wid, row_loss, Bn, stats, scratch);
     RGQA_LAUNCH_CHECK("resample_owner_kernel");
     const int G = (int)(((int64_t)N + RS_CHUNK - 1) / RS_CHUNK);
-    hipLaunchKernelGGL(resample_step_kernel, dim3(G), dim3(RS_T), 0, s, theta, buf, N, Bn, (const float*)scratch, lr, momentum, grad_out, rs_vec_ok(theta, 0), rs_vec_ok(buf, 0),
-                       rs_vec_ok(grad_out, 0));
+    hipLaunchKernelGGL(resample_step_kernel, dim3(G), dim3(RS_T), 0, s, theta, buf, N, Bn, (const float*)scratch, lr, momentum, grad_out, vec16_ok(theta, 0), vec16_ok(buf, 0),
+                       vec16_ok(grad_out, 0));
     RGQA_LAUNCH_CHECK("resample_step_kernel");
     return RGQA_OK;
 }

@@ -81,6 +81,7 @@ int k_score_rows(const float* logits, int ld, int B, int NA, float temperature, 
 // alone; the target is max_score >= 0.5 - NOT logit >= 0: at T = 1e5 the f32 sigmoid of a small negative logit is exactly 0.5.
 // One workgroup per row writes the row of dlogits: (sigmoid(z) - y) / B at the chosen column (the un-tempered logit, as bceloss(logit, labels)
 // is), exact zeros elsewhere up to column NAp.  Workgroup 0 also folds the loss over the rows in a fixed order.
+// (not rowops.h's bce_term: that one takes __expf, this one expf - the two give different bits)
 __device__ __forceinline__ float bce_logit(float z, float y) { return fmaxf(z, 0.f) - z * y + log1pf(expf(-fabsf(z))); }
 
 __global__ __launch_bounds__(256) void odin_dlogits_kernel(const float* __restrict__ logits, int ld, const int64_t* __restrict__ label, const float* __restrict__ max_score,

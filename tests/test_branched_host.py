@@ -1,9 +1,8 @@
 """The confidence-branch model, host side (no GPU): the restatement of the reference's model and trainer statements (tests/branched_reference.py) reproduces
 the fixture of the reference's own GQAModel_branched (tests/golden/g15_branched.npz, tools/gen_g15_branched.py); the closed-form dlogits / dconf the kernel
 computes equal f64 autograd of the statements; the engine's parameter table with and without the branch; and the loss and conf-tail kernels, compiled for the
-host under a workgroup emulation as a stand-alone program (tests/branched_host_emu/), against the same statements."""
+host under a workgroup emulation as a stand-alone program (tests/host_emu/), against the same statements."""
 import os
-import shutil
 import subprocess
 
 import numpy as np
@@ -12,8 +11,7 @@ import torch
 
 from rgqa_amd import synth
 from tests import branched_reference as BR
-
-HERE = os.path.dirname(os.path.abspath(__file__))
+from tests import host_emu
 
 
 def _oracle_small(dtype):
@@ -82,26 +80,11 @@ def test_parameter_table_with_and_without_the_branch():
 
 
 # ------------------------------------------------------------------------------------------------ the kernels under a host workgroup emulation
-EMU = os.path.join(HERE, "branched_host_emu")
-
-
 @pytest.fixture(scope="module")
 def emu(tmp_path_factory):
-    """the two units built by the host compiler over tests/branched_host_emu/kernels.h as a stand-alone program, with the host sanitizers where the
+    """the two units built by the host compiler over tests/host_emu/kernels.h as a stand-alone program, with the host sanitizers where the
     toolchain has their runtimes"""
-    root = os.path.dirname(HERE)
-    d = tmp_path_factory.mktemp("branched_emu")
-    os.makedirs(d / "rgqa_amd" / "csrc")
-    for unit in ("branched_loss", "conf_head"):
-        shutil.copy(os.path.join(root, "rgqa_amd", "csrc", unit + ".hip"), d / "rgqa_amd" / "csrc" / (unit + ".cpp"))
-    shutil.copy(os.path.join(EMU, "kernels.h"), d / "rgqa_amd" / "csrc" / "kernels.h")
-    shutil.copy(os.path.join(EMU, "main.cpp"), d / "main.cpp")
-    base = ["g++", "-std=c++20", "-O1", "-pthread", "-I.", "main.cpp", "-o", "emu"]
-    r = subprocess.run(base + ["-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"], cwd=d, capture_output=True, text=True)
-    if r.returncode != 0:          # a toolchain without the sanitizer runtimes: the same program without them
-        r = subprocess.run(base, cwd=d, capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-3000:]
-    return str(d / "emu")
+    return host_emu.build(tmp_path_factory.mktemp("branched_emu"), ["branched_loss", "conf_head"], "branched.cpp")
 
 
 def _run_emu(exe, tmp_path, z, c, t, mce, NAp, w=None, x=None, dg=None, dconf=None):

@@ -95,19 +95,13 @@ def test_reference_statements_with_an_empty_subset(ood, mce):
 
 
 def test_kernels_on_the_host(tmp_path):
-    """csrc/energy_loss.hip built by the host compiler over tests/energy_host_emu/kernels.h (each workgroup = 256 threads with barriers) and run against
-    f64 loops of the reference statements (tests/energy_host_emu/main.cpp): BCE and MCE form, NA = 67 and 1842, aligned and shifted operands giving the
+    """csrc/energy_loss.hip built by the host compiler over tests/host_emu/kernels.h (each workgroup = 256 threads with barriers) and run against
+    f64 loops of the reference statements (tests/host_emu/energy.cpp): BCE and MCE form, NA = 67 and 1842, aligned and shifted operands giving the
     same bits, guard words behind every output, exact zeros in the padded columns, grad_scale 0.5 halving exactly, both empty subsets, the argument
     checks.  (`./emu full` adds the larger shapes; a minute.)"""
-    import shutil
     import subprocess
-    emu = os.path.join(ROOT, "tests", "energy_host_emu")
-    os.makedirs(tmp_path / "rgqa_amd" / "csrc")
-    shutil.copy(os.path.join(ROOT, "rgqa_amd", "csrc", "energy_loss.hip"), tmp_path / "rgqa_amd" / "csrc" / "energy_loss.cpp")
-    shutil.copy(os.path.join(emu, "kernels.h"), tmp_path / "rgqa_amd" / "csrc" / "kernels.h")
-    shutil.copy(os.path.join(emu, "main.cpp"), tmp_path / "main.cpp")
-    r = subprocess.run(["g++", "-std=c++20", "-O1", "-pthread", "-I.", "main.cpp", "-o", "emu"], cwd=tmp_path, capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-3000:]
+    from tests import host_emu
+    host_emu.build(tmp_path, ["energy_loss"], "energy.cpp")
     r = subprocess.run(["./emu"], cwd=tmp_path, capture_output=True, text=True, timeout=600)
     print(r.stdout)
     assert r.returncode == 0 and "TOTAL bad 0" in r.stdout, r.stdout[-3000:] + r.stderr[-1000:]

@@ -121,21 +121,13 @@ def test_maha_entry_points_are_declared_bound_and_exported():
 
 
 def test_kernels_on_the_host(tmp_path):
-    """csrc/maha.hip built by the host compiler over tests/maha_host_emu/kernels.h (each workgroup = 256 threads with barriers) and run on small shapes
-    against f64 loops (tests/maha_host_emu/main.cpp): both tile variants of the distance kernel, row strides, a duplicated class (first maximum), a NaN
+    """csrc/maha.hip built by the host compiler over tests/host_emu/kernels.h (each workgroup = 256 threads with barriers) and run on small shapes
+    against f64 loops (tests/host_emu/maha.cpp): both tile variants of the distance kernel, row strides, a duplicated class (first maximum), a NaN
     row, an overflowing class (-inf, never the winner), an invalid label, guard words behind scratch and state, counts exact, sums and G to 1e-12, two
     batches = the concatenated batch bit for bit."""
-    import shutil
     import subprocess
-    emu = os.path.join(ROOT, "tests", "maha_host_emu")
-    os.makedirs(tmp_path / "rgqa_amd" / "csrc")
-    os.makedirs(tmp_path / "include")
-    shutil.copy(os.path.join(ROOT, "rgqa_amd", "csrc", "maha.hip"), tmp_path / "rgqa_amd" / "csrc" / "maha.cpp")
-    shutil.copy(os.path.join(emu, "kernels.h"), tmp_path / "rgqa_amd" / "csrc" / "kernels.h")
-    shutil.copy(os.path.join(ROOT, "include", "rgqa.h"), tmp_path / "include" / "rgqa.h")
-    shutil.copy(os.path.join(emu, "main.cpp"), tmp_path / "main.cpp")
-    r = subprocess.run(["g++", "-std=c++20", "-O1", "-pthread", "-I.", "main.cpp", "-o", "emu"], cwd=tmp_path, capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-3000:]
+    from tests import host_emu
+    host_emu.build(tmp_path, ["maha"], "maha.cpp", headers=["include/rgqa.h"])
     r = subprocess.run(["./emu"], cwd=tmp_path, capture_output=True, text=True, timeout=600)
     print(r.stdout)
     assert r.returncode == 0 and "TOTAL bad 0" in r.stdout, r.stdout[-3000:] + r.stderr[-1000:]

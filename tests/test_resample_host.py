@@ -141,20 +141,14 @@ def test_closed_form_gradient_is_autograd_of_the_statements(N, Bn):
 
 
 def test_kernels_on_the_host(tmp_path):
-    """csrc/resample.hip built by the host compiler over tests/resample_host_emu/kernels.h (each workgroup = 256 threads with barriers) and run against
-    f64 loops of the reference statements and of the closed-form weight step (tests/resample_host_emu/main.cpp): N = 2, 37 and 4099 (five chunks of
+    """csrc/resample.hip built by the host compiler over tests/host_emu/kernels.h (each workgroup = 256 threads with barriers) and run against
+    f64 loops of the reference statements and of the closed-form weight step (tests/host_emu/resample.cpp): N = 2, 37 and 4099 (five chunks of
     theta, the last one partial), NA = 67 and 1842, duplicated indices, indices outside [0, N) skipped, aligned and shifted operands giving the same bits,
     guard words behind every output, exact zeros in the padded columns, grad_scale 0.5 halving exactly, the argument checks.  (`./emu full` adds
     more shapes.)"""
-    import shutil
     import subprocess
-    emu = os.path.join(ROOT, "tests", "resample_host_emu")
-    os.makedirs(tmp_path / "rgqa_amd" / "csrc")
-    shutil.copy(os.path.join(ROOT, "rgqa_amd", "csrc", "resample.hip"), tmp_path / "rgqa_amd" / "csrc" / "resample.cpp")
-    shutil.copy(os.path.join(emu, "kernels.h"), tmp_path / "rgqa_amd" / "csrc" / "kernels.h")
-    shutil.copy(os.path.join(emu, "main.cpp"), tmp_path / "main.cpp")
-    r = subprocess.run(["g++", "-std=c++20", "-O1", "-pthread", "-I.", "main.cpp", "-o", "emu"], cwd=tmp_path, capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-3000:]
+    from tests import host_emu
+    host_emu.build(tmp_path, ["resample"], "resample.cpp")
     r = subprocess.run(["./emu"], cwd=tmp_path, capture_output=True, text=True, timeout=600)
     print(r.stdout)
     assert r.returncode == 0 and "TOTAL bad 0" in r.stdout, r.stdout[-3000:] + r.stderr[-1000:]
