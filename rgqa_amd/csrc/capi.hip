@@ -418,6 +418,17 @@ int rgqa_op_layernorm_bwd(const void* dy, const void* x, const float* gamma, con
     if (dtype == 1) return k_ln_bwd<bf16_t>((const bf16_t*)dy, N, (const bf16_t*)x, N, gamma, mean, rstd, (bf16_t*)dx, nullptr, N, ws, dgamma, dbeta, nullptr, 0, M, N, nd, nd, 1.f, S(stream));
     return k_ln_bwd<float>((const float*)dy, N, (const float*)x, N, gamma, mean, rstd, (float*)dx, nullptr, N, ws, dgamma, dbeta, nullptr, 0, M, N, nd, nd, 1.f, S(stream));
 }
+// dtype 0 = f32 (generic kernels only), 1 = bf16, 2 = split f32; impl 1 = the MFMA core, 0 = the generic LDS / VALU kernels
+static int attn_fwd_op(const AttnArgs& a, int dtype, int impl, hipStream_t s) {
+    if (dtype == 2) return impl == 1 ? k_attn_fwd_mfma<sf32>(a, s) : k_attn_fwd_ref<sf32>(a, s);
+    if (dtype == 1) return impl == 1 ? k_attn_fwd_mfma<bf16_t>(a, s) : k_attn_fwd_ref<bf16_t>(a, s);
+    return k_attn_fwd_ref<float>(a, s);
+}
+static int attn_bwd_op(const AttnArgs& a, int dtype, int impl, hipStream_t s) {
+    if (dtype == 2) return impl == 1 ? k_attn_bwd_mfma<sf32>(a, s) : k_attn_bwd_ref<sf32>(a, s);
+    if (dtype == 1) return impl == 1 ? k_attn_bwd_mfma<bf16_t>(a, s) : k_attn_bwd_ref<bf16_t>(a, s);
+    return k_attn_bwd_ref<float>(a, s);
+}
 static void fill_attn(AttnArgs& a, const void* qkv, const float* mask, int B, int nh, int L, int dh, size_t esz) {
     memset(&a, 0, sizeof a);
     const int H = nh * dh;
@@ -428,9 +439,7 @@ static void fill_attn(AttnArgs& a, const void* qkv, const float* mask, int B, in
 int rgqa_op_attention(const void* qkv, const float* mask, void* out, float* lse, int B, int nh, int L, int dh, int dtype, int impl, void* stream) {
     AttnArgs a; fill_attn(a, qkv, mask, B, nh, L, dh, dtype == 1 ? 2 : 4);
     a.out = out; a.ldo = nh * dh; a.lse = lse;
-    if (dtype == 2) return impl == 1 ? k_attn_fwd_x3(a, S(stream)) : k_attn_fwd_ref<sf32>(a, S(stream));
-    if (dtype == 1) return impl == 1 ? k_attn_fwd_mfma(a, S(stream)) : k_attn_fwd_ref<bf16_t>(a, S(stream));
-    return k_attn_fwd_ref<float>(a, S(stream));
+    return attn_fwd_op(a, dtype, impl, S(stream));
 }
 int rgqa_op_attention_bwd(const void* qkv, const float* mask, const float* lse, const void* dout, void* dqkv, int B, int nh, int L, int dh, int dtype, int impl, void* stream) {
     const size_t esz = dtype == 1 ? 2 : 4;
@@ -438,9 +447,7 @@ int rgqa_op_attention_bwd(const void* qkv, const float* mask, const float* lse, 
     const int H = nh * dh;
     a.lse = const_cast<float*>(lse); a.dout = dout; a.lddo = H;
     a.dq = dqkv; a.dk = (char*)dqkv + (size_t)H * esz; a.dv = (char*)dqkv + (size_t)2 * H * esz; a.lddq = a.lddk = a.lddv = 3 * H;
-    if (dtype == 2) return impl == 1 ? k_attn_bwd_x3(a, S(stream)) : k_attn_bwd_ref<sf32>(a, S(stream));
-    if (dtype == 1) return impl == 1 ? k_attn_bwd_mfma(a, S(stream)) : k_attn_bwd_ref<bf16_t>(a, S(stream));
-    return k_attn_bwd_ref<float>(a, S(stream));
+    return attn_bwd_op(a, dtype, impl, S(stream));
 }
 static void fill_attn_rows(AttnArgs& a, const void* q, int ldq, const void* kv, int ldkv, const int* cu_q, const int* cu_k, const float* mask, int B, int nh, int Lq, int Lk, size_t esz) {
     memset(&a, 0, sizeof a);
@@ -453,9 +460,7 @@ int rgqa_op_attention_rows(const void* q, int ldq, const void* kv, int ldkv, con
                            int B, int nh, int Lq, int Lk, int dtype, int impl, void* stream) {
     AttnArgs a; fill_attn_rows(a, q, ldq, kv, ldkv, cu_q, cu_k, mask, B, nh, Lq, Lk, dtype == 1 ? 2 : 4);
     a.out = out; a.ldo = nh * 64; a.lse = lse;
-    if (dtype == 2) return impl == 1 ? k_attn_fwd_x3(a, S(stream)) : k_attn_fwd_ref<sf32>(a, S(stream));
-    if (dtype == 1) return impl == 1 ? k_attn_fwd_mfma(a, S(stream)) : k_attn_fwd_ref<bf16_t>(a, S(stream));
-    return k_attn_fwd_ref<float>(a, S(stream));
+    return attn_fwd_op(a, dtype, impl, S(stream));
 }
 int rgqa_op_attention_rows_bwd(const void* q, int ldq, const void* kv, int ldkv, const int* cu_q, const int* cu_k, const float* mask, const float* lse,
                                const void* dout, void* dq, void* dkv, int B, int nh, int Lq, int Lk, int dtype, int impl, void* stream) {
@@ -464,9 +469,7 @@ int rgqa_op_attention_rows_bwd(const void* q, int ldq, const void* kv, int ldkv,
     const int H = nh * 64;
     a.lse = const_cast<float*>(lse); a.dout = dout; a.lddo = H;
     a.dq = dq; a.lddq = H; a.dk = dkv; a.dv = (char*)dkv + (size_t)H * esz; a.lddk = a.lddv = 2 * H;
-    if (dtype == 2) return impl == 1 ? k_attn_bwd_x3(a, S(stream)) : k_attn_bwd_ref<sf32>(a, S(stream));
-    if (dtype == 1) return impl == 1 ? k_attn_bwd_mfma(a, S(stream)) : k_attn_bwd_ref<bf16_t>(a, S(stream));
-    return k_attn_bwd_ref<float>(a, S(stream));
+    return attn_bwd_op(a, dtype, impl, S(stream));
 }
 int rgqa_batch_prepare(const void* feats_in, int feats_f16, float* feats_out, const float* boxes_in, const int32_t* img_hw, float* boxes_out,
                        const int32_t* offsets, const int32_t* labels, const float* scores, float* target, int ld_target,

@@ -191,25 +191,24 @@ int g_rgqa_attn_trim = 1;      // rgqa_debug_set(23, v): 0 = every attention wav
 // RGQA_ATTN_REF (test switch: the plain attention kernels instead of the MFMA ones), read once
 static bool attn_ref_forced() { static const bool v = getenv("RGQA_ATTN_REF") != nullptr; return v; }
 // attention kernels by element type (forward: the engine's activation type; backward: its gradient type)
+// the MFMA core (attn_core.h) serves bf16_t and sf32 at head size 64; everything else runs the generic kernels
+static bool attn_mfma_serves(const AttnArgs& a) { return a.dh == 64 && !attn_ref_forced(); }
 template <typename U> static int attn_fwd_any(const AttnArgs& a, hipStream_t s) {
-    if constexpr (std::is_same<U, sf32>::value) { if (a.dh == 64 && !attn_ref_forced()) return k_attn_fwd_x3(a, s); }
-    else if constexpr (std::is_same<U, bf16_t>::value) { if (a.dh == 64 && !attn_ref_forced()) return k_attn_fwd_mfma(a, s); }
+    if constexpr (!std::is_same<U, float>::value) { if (attn_mfma_serves(a)) return k_attn_fwd_mfma<U>(a, s); }
     return k_attn_fwd_ref<U>(a, s);
 }
 template <typename U> static int attn_bwd_any(const AttnArgs& a, hipStream_t s) {
-    if constexpr (std::is_same<U, sf32>::value) { if (a.dh == 64 && !attn_ref_forced()) return k_attn_bwd_x3(a, s); }
-    else if constexpr (std::is_same<U, bf16_t>::value) { if (a.dh == 64 && !attn_ref_forced()) return k_attn_bwd_mfma(a, s); }
+    if constexpr (!std::is_same<U, float>::value) { if (attn_mfma_serves(a)) return k_attn_bwd_mfma<U>(a, s); }
     return k_attn_bwd_ref<U>(a, s);
 }
+// 1 = launched, 0 = launch the two problems separately, < 0 = error
 template <typename U> static int attn_fwd_pair_any(const AttnArgs& a0, const AttnArgs& a1, hipStream_t s) {
-    if constexpr (std::is_same<U, sf32>::value) return (a0.dh == 64 && !attn_ref_forced()) ? k_attn_fwd_x3_pair(a0, a1, s) : 0;
-    else if constexpr (std::is_same<U, bf16_t>::value) return (a0.dh == 64 && !attn_ref_forced()) ? k_attn_fwd_mfma_pair(a0, a1, s) : 0;
-    else return 0;
+    if constexpr (!std::is_same<U, float>::value) { if (attn_mfma_serves(a0)) return k_attn_fwd_mfma_pair<U>(a0, a1, s); }
+    return 0;
 }
 template <typename U> static int attn_bwd_pair_any(const AttnArgs& a0, const AttnArgs& a1, hipStream_t s) {
-    if constexpr (std::is_same<U, sf32>::value) return (a0.dh == 64 && !attn_ref_forced()) ? k_attn_bwd_x3_pair(a0, a1, s) : 0;
-    else if constexpr (std::is_same<U, bf16_t>::value) return (a0.dh == 64 && !attn_ref_forced()) ? k_attn_bwd_mfma_pair(a0, a1, s) : 0;
-    else return 0;
+    if constexpr (!std::is_same<U, float>::value) { if (attn_mfma_serves(a0)) return k_attn_bwd_mfma_pair<U>(a0, a1, s); }
+    return 0;
 }
 
 // T = type of the activations the FORWARD pass computes in (and of the direct weight operand copy).  MIXED (T = sf32 only; rgqa.h

@@ -67,7 +67,7 @@ struct AttnArgs {
     int Lq = (a).Lq, Lk = (a).Lk;                                                                \
     if ((a).cu_q) { const int c0_ = (a).cu_q[(b)]; q0 = (size_t)c0_; Lq = (a).cu_q[(b) + 1] - c0_; } \
     if ((a).cu_k) { const int c0_ = (a).cu_k[(b)]; k0 = (size_t)c0_; Lk = (a).cu_k[(b) + 1] - c0_; }
-// ---- shared by the MFMA cores (attn_mfma.hip, attn_x3.hip): one wave per (sample, head), instruction-issue bound
+// ---- the MFMA core (attn_core.h; instantiated by attn_mfma.hip and attn_x3.hip): one wave per (sample, head), instruction-issue bound
 // Per-sample tile counts (rgqa_debug_set key 23; 1 = default): with packed rows a wave knows its own sample's Lq / Lk, and a sample that fills one
 // 16-row tile fewer than the launch's <NQT, NKT> in a dimension runs the body instantiated for that count.  Every dimension is trimmed by at most ONE
 // tile (<= 4 bodies per problem: the 20- and 30-token questions of GQA run <1,*> / <*,1> bodies when they have <= 16 tokens, UNITER's 56-row sequences
@@ -97,7 +97,7 @@ extern int g_rgqa_attn_trim;
 #endif
 // Row addressing without per-fragment 64-bit products (v_mul_lo_u32 / v_mad_u64_u32 issue at quarter rate): the sample's first row and the head go into
 // a wave-uniform 64-bit base (scalar arithmetic), a lane adds the 32-bit byte offset row * (row pitch in bytes) + (its bytes inside the row) of at most
-// 63 rows: ONE full-rate 24-bit multiply-add.  Rows past the sample's length are read from its last valid row (see ldfrag).  The launchers reject row
+// 63 rows: ONE full-rate 24-bit multiply-add.  Rows past the sample's length are read from its last valid row (attn_core.h ldfrag).  The launchers reject row
 // strides of ATTN_MAX_LD elements or more: below it the pitch in bytes (<= 4 per element) fits the 24-bit multiply and 64 rows of it fit 32 bits,
 // whatever the tensor's total extent is.
 #define ATTN_MAX_LD (1 << 22)
@@ -126,16 +126,14 @@ __device__ __forceinline__ uint32_t attn_row_off(int row, int nrows, uint32_t pi
 template <typename T> int k_attn_fwd_ref(const AttnArgs& a, hipStream_t s);
 template <typename T> int k_attn_bwd_ref(const AttnArgs& a, hipStream_t s);
 template <typename T> int k_attn_probs(const AttnArgs& a, float* out /* [B, nh, Lq, Lk] */, hipStream_t s);
-int k_attn_fwd_mfma(const AttnArgs& a, hipStream_t s);   // bf16 only
-int k_attn_bwd_mfma(const AttnArgs& a, hipStream_t s);   // bf16 only
-int k_attn_fwd_x3(const AttnArgs& a, hipStream_t s);     // split f32 (attn_x3.hip): every product as hi*hi + hi*lo + lo*hi on the bf16 matrix pipe
-int k_attn_bwd_x3(const AttnArgs& a, hipStream_t s);
+// MFMA core (attn_core.h), by element type: U = bf16_t (instantiated in attn_mfma.hip) or sf32 (attn_x3.hip: every product as hi*hi + hi*lo + lo*hi on the
+// bf16 matrix pipe)
+template <typename U> int k_attn_fwd_mfma(const AttnArgs& a, hipStream_t s);
+template <typename U> int k_attn_bwd_mfma(const AttnArgs& a, hipStream_t s);
 // the two attention problems of a stage (language | vision, or the two cross directions) in ONE launch: 1 = launched, 0 = shapes not covered
 // (launch them separately), < 0 = error
-int k_attn_fwd_mfma_pair(const AttnArgs& a0, const AttnArgs& a1, hipStream_t s);
-int k_attn_bwd_mfma_pair(const AttnArgs& a0, const AttnArgs& a1, hipStream_t s);
-int k_attn_fwd_x3_pair(const AttnArgs& a0, const AttnArgs& a1, hipStream_t s);
-int k_attn_bwd_x3_pair(const AttnArgs& a0, const AttnArgs& a1, hipStream_t s);
+template <typename U> int k_attn_fwd_mfma_pair(const AttnArgs& a0, const AttnArgs& a1, hipStream_t s);
+template <typename U> int k_attn_bwd_mfma_pair(const AttnArgs& a0, const AttnArgs& a1, hipStream_t s);
 
 // ---- embed.hip
 // lang[b*T+t] = dropout(LN(word[ids] + pos[t] + type[seg]))      (reference BertEmbeddings, modeling.py:278-292)

@@ -1,4 +1,4 @@
-"""Per-sample tile counts of the MFMA attention kernels (rgqa_debug_set key 23; attn_mfma.hip, attn_x3.hip, kernels.h ATTN_RUN_TRIMMED).
+"""Per-sample tile counts of the MFMA attention kernels (rgqa_debug_set key 23; attn_core.h and its units attn_mfma.hip, attn_x3.hip, kernels.h ATTN_RUN_TRIMMED).
 
 With packed rows a wave whose sample fills one 16-row tile fewer than its launch's tile counts runs the body of the smaller count.  What it
 leaves out only ever held masked keys (probabilities exactly 0) and query rows that are never stored, so every result must be BIT-identical

@@ -1,9 +1,11 @@
-"""Static instruction counts of the attention kernels: compiles attn_x3.hip and attn_mfma.hip to gfx950 assembly with the flags of
+"""Static instruction counts of the attention kernels: compiles attn_x3.hip and attn_mfma.hip (the split-f32 and the bf16 instantiation of
+csrc/attn_core.h, where the kernels' code lives; before that header each unit held its own copy) to gfx950 assembly with the flags of
 rgqa_amd/build.py and prints, per kernel, what the instruction-issue cost is made of (no GPU needed):
 
     python tools/attn_isa_counts.py [name-filter] [--md] [--notrim] [--csrc=DIR]
 
---csrc=DIR reads the two units (and their headers) from DIR instead of rgqa_amd/csrc: another commit's sources beside this tree's.
+--csrc=DIR reads the two units (and their headers) from DIR instead of rgqa_amd/csrc: another commit's sources beside this tree's, with or
+without attn_core.h - the kernels keep their names, which is all short() relies on.
 
 columns: instructions (everything between the kernel's label and its last s_endpgm), VALU (v_* other than MFMA), v_mul_lo_u32 (+ v_mad_u64_u32:
 the quarter-rate integer multiplies), MFMA, s_nop, VGPR + AGPR, LDS bytes, scratch bytes, waves per SIMD (the compiler's occupancy figure).
