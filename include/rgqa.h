@@ -51,7 +51,18 @@ typedef struct rgqa_config {
     int32_t emb_dim;  /* BUTD word-embedding size (300) */
     int32_t conf_branch; /* arch 0 only, default 0: 1 = GQAModel_branched (tasks/gqa_model_branched.py:14-51): a second head conf_fc = Linear(H, 2H) -> GeLU ->
                             LayerNorm(2H) -> Linear(2H, 1) on the pooled vector.  Six tensors conf_fc.0 / .2 / .3 .weight / .bias follow logit_fc.3 in the parameter
-                            table (conf_fc.3 is read from the f32 master arena); with 0 the table and every result are unchanged */
+                            table (conf_fc.3 is read from the f32 master arena); with 0 the table and every result are unchanged.
+                            2 = the layer-wise branch (tasks/gqa_branched_layer.py:47-59, :280-320), x_layers >= 1: the head reads EVERY cross-modality layer - the
+                            [CLS] row of layer i's language output goes through projs.<i>.proj.0 = Linear(H, P) -> Tanh, the X projections side by side [B, X P] through
+                            conf_fc = Linear(X P, 2 X P) -> GeLU -> LayerNorm(2 X P) -> Linear(2 X P, 1), with P = project_size below.  Behind logit_fc.3 the table holds
+                            projs.<i>.proj.0.weight [P, H] / .bias [P] for i = 0 .. X - 1, then conf_fc.0 [2 X P, X P], conf_fc.2 [2 X P], conf_fc.3 [1, 2 X P] (read
+                            from the f32 master arena) with their biases.  The entry points of the branch keep their meaning; the gradient of tap i enters the ONE
+                            encoder backward in front of layer i's FFN stage */
+    int32_t project_size; /* read only when conf_branch == 2 (the reference's --project_size, param.py:57: 128).  Accepted: a multiple of 8 in the f32 and bf16
+                            precisions, a multiple of 32 in bf16x3 / bf16x3_fwd (a projector's slice of a [B, X P] row is a GEMM operand of its own: whole 16-byte
+                            chunks, whole 128-byte split-f32 lines), with x_layers <= 12 (the X projector GEMMs are one grouped launch) and 2 * x_layers *
+                            project_size <= 2048 (the conf tail's row); anything else is refused by rgqa_engine_create.  With project_size and x_layers * project_size
+                            multiples of 64 - 128 at 5 layers - every launch of the branch runs on the LDS-DMA GEMM kernels (none takes the 128 x 128 kernel) */
 } rgqa_config;
 
 typedef struct rgqa_engine rgqa_engine;
@@ -162,20 +173,28 @@ int rgqa_engine_backward(rgqa_engine* e, const float* dlogits, int ld, int accum
  * weight_g and weight_v - the tail of the arena), accumulate = 1 leaves it as it is, so rgqa_engine_backward followed by this call with
  * accumulate = 1 after ONE forward gives the gradient of a loss that reads both outputs.  Honours rgqa_engine_set_input_grads. */
 int rgqa_engine_backward_pooled(rgqa_engine* e, const float* dpooled, int ld, int accumulate, void* stream);
-/* ---- the confidence branch (rgqa_config.conf_branch = 1).  The forward pass also leaves conf_logit [B] f32 = conf_fc(pooled) (the conf_fc.0 GEMM in the
- * engine's forward precision, GeLU / LayerNorm statistics / the 2H -> 1 dot in f32); rgqa_engine_get_conf copies it out. */
+/* ---- the confidence branch.  The forward pass also leaves conf_logit [B] f32; rgqa_engine_get_conf copies it out.
+ *   conf_branch = 1: conf_logit = conf_fc(pooled) - the conf_fc.0 GEMM (H -> 2H) in the engine's forward precision, GeLU / LayerNorm statistics / the 2H -> 1 dot
+ *                    in f32.  The tensors of the branch are the six conf_fc tensors.
+ *   conf_branch = 2: conf_logit = conf_fc(cat_i tanh(projs.<i>(x<i>_lang[:, 0]))) - the X projector GEMMs (H -> P, one grouped launch) and the conf_fc.0 GEMM
+ *                    (X P -> 2 X P) in the engine's forward precision, GeLU / LayerNorm statistics / the 2 X P -> 1 dot in f32.  The tensors of the branch are
+ *                    projs.<i>.proj.0.weight / .bias (i < X) and the six conf_fc tensors.
+ * "The tensors of the branch" below means those. */
 int rgqa_engine_get_conf(rgqa_engine* e, float* conf_logit_out, void* stream);
+/* conf_branch = 2: the X projections of the last forward side by side, [B, x_layers * project_size] f32 with row stride ld (>= that width) - tanh outputs,
+ * column block i = projs.<i> on the [CLS] row of cross-modality layer i's language output */
+int rgqa_engine_get_layer_proj(rgqa_engine* e, float* out, int ld, void* stream);
 /* backward from dL/dlogits [B, num_answers] f32 (row stride ld) and dL/dconf_logit [B] f32 after ONE forward, in ONE encoder backward pass: the conf head's
  * share is added to d(pooler pre-tanh) before the encoder's backward starts.  Either gradient may be NULL = zeros.  On an engine without the branch dconf
  * must be NULL and the call is rgqa_engine_backward.  Honours rgqa_engine_set_input_grads. */
 int rgqa_engine_backward2(rgqa_engine* e, const float* dlogits, int ld, const float* dconf, int accumulate, void* stream);
-/* backward from dL/dconf_logit [B] f32 into the six conf_fc tensors ALONE (the conf_only path below with a caller-supplied gradient: a model whose answer
+/* backward from dL/dconf_logit [B] f32 into the tensors of the branch ALONE (the conf_only path below with a caller-supplied gradient: a model whose answer
  * branch and encoder are frozen under autograd): no answer-head or encoder backward; accumulate = 0 leaves exact zeros everywhere else. */
 int rgqa_engine_backward_conf(rgqa_engine* e, const float* dconf, int accumulate, void* stream);
 /* The train step of the branched trainer (tasks/gqa_branched.py:126-143): rgqa_op_branched_loss (below) on the last forward's logits and conf logits +
  * backward into the grad arena.  target_with_uq [B, ld_target >= num_answers + 1] f32, column num_answers = the UQ flag (non-zero = unanswerable).
  * loss3 (3 floats: loss, loss_ce, loss_conf), conf [B] = sigmoid(conf_logit), label [B] int64: device buffers, each may be NULL.  After the call the gradient
- * arena has the bits of rgqa_engine_backward2 on the operator's dlogits and dconf.  conf_only != 0 (--freeze_vqa_branch): only the six conf_fc tensors receive
+ * arena has the bits of rgqa_engine_backward2 on the operator's dlogits and dconf.  conf_only != 0 (--freeze_vqa_branch): only the tensors of the branch receive
  * gradients - neither the answer head's nor the encoder's backward is launched; accumulate = 0 then leaves exact zeros everywhere else. */
 int rgqa_engine_branched_loss_backward(rgqa_engine* e, const float* target_with_uq, int ld_target, int mce, float grad_scale, int conf_only, float* loss3,
                                        float* conf, int64_t* label, int accumulate, void* stream);

@@ -11,7 +11,8 @@ PREC_F32, PREC_BF16, PREC_BF16X3, PREC_BF16X3_FWD = 0, 1, 2, 3
 class Config(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("vocab_size", "hidden", "heads", "inter", "max_pos", "type_vocab", "l_layers",
                                          "x_layers", "r_layers", "feat_dim", "pos_dim", "num_answers", "precision")] + \
-               [("ln_eps", C.c_float), ("hidden_dropout", C.c_float), ("attn_dropout", C.c_float), ("arch", C.c_int32), ("emb_dim", C.c_int32), ("conf_branch", C.c_int32)]
+               [("ln_eps", C.c_float), ("hidden_dropout", C.c_float), ("attn_dropout", C.c_float), ("arch", C.c_int32), ("emb_dim", C.c_int32), ("conf_branch", C.c_int32),
+                ("project_size", C.c_int32)]
 
 
 _vp, _sz, _i, _f, _u64 = C.c_void_p, C.c_size_t, C.c_int, C.c_float, C.c_uint64
@@ -41,6 +42,7 @@ SIGNATURES = {
     "rgqa_engine_backward": [_vp, _vp, _i, _i, _vp],
     "rgqa_engine_backward_pooled": [_vp, _vp, _i, _i, _vp],
     "rgqa_engine_get_conf": [_vp, _vp, _vp],
+    "rgqa_engine_get_layer_proj": [_vp, _vp, _i, _vp],
     "rgqa_engine_backward2": [_vp, _vp, _i, _vp, _i, _vp],
     "rgqa_engine_backward_conf": [_vp, _vp, _i, _vp],
     "rgqa_engine_branched_loss_backward": [_vp, _vp, _i, _i, _f, _i, _vp, _vp, _vp, _i, _vp],

@@ -65,8 +65,17 @@ int rgqa_debug_set(int key, int value) {
 
 int rgqa_engine_create(const rgqa_config* cfg, rgqa_engine** out) {
     RGQA_REQUIRE(cfg != nullptr && out != nullptr, "engine_create: null argument");
-    RGQA_REQUIRE(cfg->conf_branch == 0 || cfg->conf_branch == 1, "engine_create: conf_branch must be 0 or 1 (got %d)", cfg->conf_branch);
-    RGQA_REQUIRE(cfg->conf_branch == 0 || cfg->arch == 0, "engine_create: the confidence branch (conf_branch = 1) exists on the LXMERT engine only (arch 0); got arch %d", cfg->arch);
+    RGQA_REQUIRE(cfg->conf_branch >= 0 && cfg->conf_branch <= 2, "engine_create: conf_branch must be 0, 1 or 2 (got %d)", cfg->conf_branch);
+    RGQA_REQUIRE(cfg->conf_branch == 0 || cfg->arch == 0, "engine_create: the confidence branch (conf_branch = %d) exists on the LXMERT engine only (arch 0); got arch %d", cfg->conf_branch, cfg->arch);
+    if (cfg->conf_branch == 2) {
+        // what the GEMM family takes (rgqa.h): slice i of the [B, X P] projection matrix is an operand of its own - 16-byte aligned rows in f32 / bf16, whole
+        // 128-byte lines in split f32; X problems in one NT launch; the conf tail's row of 2 X P values in one workgroup
+        const int P = cfg->project_size, X = cfg->x_layers;
+        const bool x3 = cfg->precision == RGQA_PRECISION_BF16X3 || cfg->precision == RGQA_PRECISION_BF16X3_FWD;
+        RGQA_REQUIRE(X >= 1 && X <= TAP_MAX_LAYERS, "engine_create: the layer-wise confidence branch (conf_branch = 2) needs 1 .. %d cross-modality layers (x_layers = %d)", TAP_MAX_LAYERS, X);
+        RGQA_REQUIRE(P >= 8 && P % (x3 ? 32 : 8) == 0, "engine_create: project_size %d unsupported: a positive multiple of %d in this precision (8 in f32 / bf16, 32 in bf16x3 / bf16x3_fwd)", P, x3 ? 32 : 8);
+        RGQA_REQUIRE((long)2 * X * P <= 2048, "engine_create: project_size %d unsupported: 2 * x_layers * project_size = %ld exceeds 2048, the widest row of the conf tail", P, (long)2 * X * P);
+    }
     if (cfg->arch == 1) {
         RGQA_REQUIRE(cfg->hidden > 0 && cfg->hidden % 64 == 0 && cfg->emb_dim > 0 && cfg->vocab_size > 1 && cfg->num_answers > 0 && cfg->feat_dim % 4 == 0 &&
                      cfg->pos_dim >= 1 && cfg->pos_dim <= 4, "engine_create (BUTD): hidden %% 64, emb_dim, vocab_size, num_answers, feat_dim %% 4 required");
@@ -164,6 +173,10 @@ int rgqa_engine_get_conf(rgqa_engine* e, float* conf_logit_out, void* stream) {
     NEED(e);
     RGQA_REQUIRE(conf_logit_out != nullptr, "get_conf: null argument");
     return e->impl->get_conf(conf_logit_out, S(stream));
+}
+int rgqa_engine_get_layer_proj(rgqa_engine* e, float* out, int ld, void* stream) {
+    NEED(e);
+    return e->impl->get_layer_proj(out, ld, S(stream));
 }
 int rgqa_engine_backward2(rgqa_engine* e, const float* dlogits, int ld, const float* dconf, int accumulate, void* stream) {
     NEED(e);

@@ -116,9 +116,13 @@ public:
     virtual int resample_loss_backward(const float* target, int ldt, int n_pos, const float* weights, float grad_scale, float* loss3, float* row_loss, int accumulate,
                                        hipStream_t s) = 0;
     virtual int backward(const float* dlogits, int ldd, int accumulate, hipStream_t s) = 0;
-    // the confidence branch (rgqa_config.conf_branch = 1; engine.hip): conf logits of the last forward [B]; backward from dlogits and dconf (either may be null =
-    // zeros) in ONE pass; the loss head of the branched trainer (branched_loss.hip) + that backward (conf_only: the six conf_fc tensors alone)
+    // the confidence branch (engine.hip).  rgqa_config.conf_branch = 1: conf_fc on the pooled vector, six tensors; = 2: the layer-wise one - X projectors
+    // projs.<i> on the [CLS] row of every cross-modality layer in front of a conf_fc over the X projections.  In both: conf logits of the last forward [B]; backward
+    // from dlogits and dconf (either may be null = zeros) in ONE pass; the loss head of the branched trainer (branched_loss.hip) + that backward (conf_only: the
+    // tensors of the branch alone - conf_fc.* with 1, projs.* and conf_fc.* with 2)
     virtual int get_conf(float*, hipStream_t) { rgqa_set_error("get_conf: this engine has no confidence branch (rgqa_config.conf_branch)"); return RGQA_ERR_ARG; }
+    // conf_branch = 2: the X projections side by side [B, x_layers * project_size] as f32 (row stride ld)
+    virtual int get_layer_proj(float*, int, hipStream_t) { rgqa_set_error("get_layer_proj: this engine has no layer-wise confidence branch (rgqa_config.conf_branch = 2)"); return RGQA_ERR_ARG; }
     virtual int backward2(const float* dlogits, int ldd, const float* dconf, int accumulate, hipStream_t s) {
         if (dconf != nullptr || dlogits == nullptr) { rgqa_set_error("backward2: this engine has no confidence branch (rgqa_config.conf_branch)"); return RGQA_ERR_ARG; }
         return backward(dlogits, ldd, accumulate, s);

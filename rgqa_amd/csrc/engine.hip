@@ -19,6 +19,7 @@ struct ModelParams {
     std::vector<AttP> x_cross, x_latt, x_vatt; std::vector<FfnP> x_lffn, x_vffn;
     Lin pooler, head0; LNp head_ln; Lin head3;
     Lin conf0; LNp conf_ln; Lin conf3;      // conf_branch: conf_fc.0 / .2 / .3 (tasks/gqa_model_branched.py:28-33)
+    std::vector<Lin> projs;                 // conf_branch = 2: projs.<i>.proj.0, one per cross-modality layer (tasks/gqa_branched_layer.py:47-59)
 };
 
 struct TableBuilder {
@@ -145,11 +146,21 @@ static void build_params(const rgqa_config& c, std::vector<ParamInfo>& tab, Mode
     mp.head3 = tb.lin("logit_fc.3", c.num_answers, 2 * H);
     if (c.conf_branch) {
         // behind the answer head, inside the head + pooler gradient segment (build_grad_segments: [pooler, end of the arena))
-        mp.conf0 = tb.lin("conf_fc.0", 2 * H, H);
-        mp.conf_ln = tb.ln("conf_fc.2", 2 * H);
+        // conf_branch = 2 (tasks/gqa_branched_layer.py:280-291): the head reads X projections of P values instead of the pooled vector; the projectors come
+        // first, so "everything in front of the branch" stays ONE range of the arena (backward_conf_only)
+        int cin = H;
+        if (c.conf_branch == 2) {
+            for (int i = 0; i < c.x_layers; ++i) {
+                snprintf(buf, sizeof buf, "projs.%d.proj.0", i);
+                mp.projs.push_back(tb.lin(buf, c.project_size, H));
+            }
+            cin = c.x_layers * c.project_size;
+        }
+        mp.conf0 = tb.lin("conf_fc.0", 2 * cin, cin);
+        mp.conf_ln = tb.ln("conf_fc.2", 2 * cin);
         // one output row: a row dot product on the f32 masters (conf_head.hip), no operand copies and no [2H, 64] transposed slot
-        mp.conf3.out = 1; mp.conf3.in = 2 * H; mp.conf3.ldt = 64;
-        mp.conf3.w = tb.add("conf_fc.3.weight", 1, 2 * H, 2, 0, 1); tb.read_as_f32(mp.conf3.w);
+        mp.conf3.out = 1; mp.conf3.in = 2 * cin; mp.conf3.ldt = 64;
+        mp.conf3.w = tb.add("conf_fc.3.weight", 1, 2 * cin, 2, 0, 1); tb.read_as_f32(mp.conf3.w);
         mp.conf3.b = tb.add("conf_fc.3.bias", 1, 0, 1, 64, 0);
     }
     total = rup(tb.cur, 64);
@@ -161,6 +172,7 @@ static void build_params(const rgqa_config& c, std::vector<ParamInfo>& tab, Mode
 // sat 0.17 ms per step waiting for the set of two periods ago (profiles/r02_timeline_b256.txt); with four it runs on and the side stream
 // catches up beside the longer chains of the paired layers that follow.
 #define NPAR 8
+static_assert(TAP_MAX_LAYERS <= GEMM_NT_MAX_PROBLEMS, "the X projector GEMMs (and the X tap dgrads) of the layer-wise confidence branch are the problems of ONE NT launch");
 #define WGRAD_MERGE_MAX 4      // periods of backward whose weight-gradient problems may share one launch (NPAR >= 2 * WGRAD_MERGE_MAX)
 #define SUMSQ_WS_STRIDE 1088     // k_sumsq_owned: 1024 block partials + the ticket word, per gradient segment
 #define LNPART_BLOCKS 1536     // per layer: <= 3 LayerNorm-backward launches of <= 512 blocks
@@ -281,6 +293,18 @@ public:
     // its share of d(pooler pre-tanh), dL/dconf_logit of the pass being run (dconf_ready: an entry point filled it; otherwise zeros)
     T *c1dg = nullptr, *c1 = nullptr; float *cf_mean = nullptr, *cf_rstd = nullptr, *conf_logit = nullptr;
     TB *gc3 = nullptr, *gcp = nullptr; float* dconf_dev = nullptr; bool dconf_ready = false;
+    // layer-wise branch (conf_branch = 2): the [CLS] row of every cross-modality layer's language output [X, B, H], the X projections side by side [B, X P] (the
+    // input of conf_fc.0); backward: the gradient entering the projectors' tanh [B, X P] and the gradient of every tap [X, B, H], which backward_encoder adds
+    // to the [CLS] rows of the gradient layer i's FFN stage is about to consume (inject_tap)
+    T *taps = nullptr, *projcat = nullptr; TB *dpc = nullptr, *dtap = nullptr;
+    bool layer_branch() const { return cfg.conf_branch == 2; }
+    int conf_in() const { return layer_branch() ? cfg.x_layers * cfg.project_size : cfg.hidden; }       // conf_fc.0: Linear(conf_in, conf_width)
+    int conf_width() const { return 2 * conf_in(); }
+    // The branch's weight-gradient problems (X projectors + conf_fc.0) as a launch of their OWN: riding in the head's group they would decide which kernel
+    // and tile height the head's and the last layer's problems get (their operand pitches X P and P differ from every shape of the plain engine), and those
+    // gradients must keep the plain engine's bits.  With an encoder backward the launch is deferred to the side stream with the encoder's first one
+    // (launch_pending); the conf_only pass issues the same group on the caller's stream - the same kernel, the same bits.
+    GemmGroup wg_conf;
     TB *gA = nullptr, *gB = nullptr, *gctx = nullptr;
     TB *gz_s[NPAR][3] = {}, *gzd_s[NPAR][3] = {}, *gqkv_s[NPAR][3] = {}, *gh_s[NPAR][3] = {};   // [ring position of the launch period][stage slot]
     hipStream_t s_w = nullptr;                 // side stream: the deferred weight-gradient GEMMs of a layer run beside the next layer's chain
@@ -326,6 +350,7 @@ public:
         cfg = c;
         joint = cfg.arch == 2;
         build_params(cfg, params, mp, arena_elems, dead_begin, dead_end);
+        gg_init(wg_conf);
         build_transpose_table();
         build_grad_segments();
     }
@@ -417,6 +442,10 @@ public:
         for (int k = 0; k < pend_n; ++k) if (int r = fin_flush(pend_fin[k], pend_acc[k], st)) return r;
         if (int r = run_wgrad(wgm, st)) return r;
         gg_init(wgm);
+        if (wg_conf.count > 0) {       // the layer-wise branch's weight gradients: part of the head + pooler segment, which the first launch finalises
+            if (int r = run_wgrad(wg_conf, st)) return r;
+            gg_init(wg_conf);
+        }
         sq_defer = true;
         for (int k = 0; k < pend_marks; ++k) if (int r = mark_segment(st)) { sq_defer = false; return r; }
         sq_defer = false;
@@ -501,6 +530,7 @@ public:
         for (auto& f : mp.x_lffn) addffn(f);
         for (auto& f : mp.x_vffn) addffn(f);
         add(mp.pooler); add(mp.head0); add(mp.head3);
+        for (auto& l : mp.projs) add(l);
         if (cfg.conf_branch) add(mp.conf0);
         n_tdesc = (int)tdesc_host.size();
         n_tdesc_min = (int)tdesc_min_host.size();
@@ -599,8 +629,10 @@ public:
         hd_mean = take<float>(B); hd_rstd = take<float>(B);
         logits = take<float>((size_t)B * NAp);
         if (cfg.conf_branch) {
-            c1dg = take<T>((size_t)B * 2 * H); c1 = take<T>((size_t)B * 2 * H);
+            const size_t cw = conf_width();
+            c1dg = take<T>((size_t)B * cw); c1 = take<T>((size_t)B * cw);
             cf_mean = take<float>(B); cf_rstd = take<float>(B); conf_logit = take<float>(B);
+            if (layer_branch()) { taps = take<T>((size_t)cfg.x_layers * B * H); projcat = take<T>((size_t)B * conf_in()); }
         }
         if (joint) {      // UNITER front-end: its forward tensors (they have bf16 images under MIXED) before the mark below
             const size_t ni = (size_t)B * Oi;
@@ -627,7 +659,8 @@ public:
                 gqkv_s[par][k] = take<TB>((size_t)RC * 3 * H); gh_s[par][k] = take<TB>((size_t)RC * I);
             }
         gp1 = take<TB>((size_t)B * 2 * H); gp2 = take<TB>((size_t)B * 2 * H); gp3 = take<TB>((size_t)B * 2 * H);
-        if (cfg.conf_branch) { gc3 = take<TB>((size_t)B * 2 * H); gcp = take<TB>((size_t)B * H); dconf_dev = take<float>(B); }
+        if (cfg.conf_branch) { gc3 = take<TB>((size_t)B * conf_width()); gcp = take<TB>((size_t)B * H); dconf_dev = take<float>(B); }
+        if (layer_branch()) { dpc = take<TB>((size_t)B * conf_in()); dtap = take<TB>((size_t)cfg.x_layers * B * H); }
         size_t pw = 2 * (size_t)H; if ((size_t)I > pw) pw = I; if (3 * (size_t)H > pw) pw = 3 * (size_t)H; if ((size_t)NAp > pw) pw = NAp;
         part_floats = (size_t)512 * 10 * pw;
         part = take<float>(part_floats);
@@ -778,7 +811,10 @@ public:
     }
     // dx[rows, in] = dy[rows, cols] @ W[wrow0 : wrow0+cols, :]      ; DGRAD
     bool dgrad_mixed = false;      // a group mixing [K, N] and [N, K] weight operands was built (never for the encoder's layer shapes): run_dgrad refuses it
-    void add_dgrad(GemmGroup& g, const void* dy, int lddy, const Lin& l, int wrow0, int wrows, void* dx, int lddx, int M, int epi, const void* aux, int ldaux, bool allow_nn = true) {
+    // exact_k: contract over exactly `wrows` columns of dy even on the transposed copy (whose default rounds the last block up to a whole K-step, which needs
+    // dy zero-padded up to ldt): for a dy that is a column block of a wider matrix, where the columns behind it belong to the next block
+    void add_dgrad(GemmGroup& g, const void* dy, int lddy, const Lin& l, int wrow0, int wrows, void* dx, int lddx, int M, int epi, const void* aux, int ldaux, bool allow_nn = true,
+                   bool exact_k = false) {
         GemmProblem& p = g.p[g.count++];
         memset(&p, 0, sizeof p);
         p.A = dy; p.lda = lddy; p.M = M; p.N = l.in; p.C = dx; p.ldc = lddx;
@@ -791,7 +827,7 @@ public:
             // Under the [K, N] regime only the minimal table's copies are current: anything else here is a bug of the caller
             const bool has_copy = !nn_synced || &l == &mp.visn_fc || !dgrad_nn_shape(l, l.out);
             if (g.b_kn || !has_copy) dgrad_mixed = true;
-            p.B = PbT + l.w + wrow0; p.ldb = l.ldt; p.K = (wrow0 + wrows == l.out) ? (int)rup(wrows, 64) : wrows; if (p.K > l.ldt - wrow0) p.K = l.ldt - wrow0;
+            p.B = PbT + l.w + wrow0; p.ldb = l.ldt; p.K = (wrow0 + wrows == l.out && !exact_k) ? (int)rup(wrows, 64) : wrows; if (p.K > l.ldt - wrow0) p.K = l.ldt - wrow0;
         }
         else { p.B = P + l.w + (size_t)wrow0 * l.in; p.ldb = l.in; p.K = wrows; }
         p.aux = aux; p.ldaux = ldaux; p.epi = epi;
@@ -1148,9 +1184,27 @@ public:
             if (cfg.conf_branch) {
                 // a launch of its own behind the answer head's: the head's launches stay what the plain engine issues, bit for bit
                 gg_init(g);
-                add_fwd(g, pooled, H, mp.conf0, 0, 2 * H, c1, 2 * H, B, EPI_GELU, nullptr, 0, c1dg, 0);
+                const int cin = conf_in(), cw = conf_width();
+                const T* cx = pooled;
+                if (layer_branch()) {
+                    // taps -> X projections (tanh) side by side: ONE gather launch, ONE grouped GEMM launch of X problems on the B [CLS] rows
+                    const int X = cfg.x_layers, Pz = cfg.project_size;
+                    const int nlr = cfg.l_layers > cfg.r_layers ? cfg.l_layers : cfg.r_layers;
+                    TapSrcs ts; memset(&ts, 0, sizeof ts);
+                    for (int i = 0; i < X; ++i) {
+                        const Stage& f = stages[2 * nlr + 3 * i + 2];        // what get_activation("x<i>_lang") serves
+                        ts.p[i] = f.sb[0].y; ts.compact[i] = cls_tail(f) ? 1 : 0;
+                    }
+                    CKP(PC_OTHER, k_tap_gather(ts, X, B, cu, Tn, (int)(H * sizeof(T)), taps, img(taps), s));
+                    for (int i = 0; i < X; ++i)
+                        add_fwd(g, taps + (size_t)i * B * H, H, mp.projs[i], 0, Pz, projcat + (size_t)i * Pz, cin, B, EPI_TANH, nullptr, 0, nullptr, 0);
+                    CK(run_fwd(g, s, 0, 0, true));
+                    gg_init(g);
+                    cx = projcat;
+                }
+                add_fwd(g, cx, cin, mp.conf0, 0, cw, c1, cw, B, EPI_GELU, nullptr, 0, c1dg, 0);
                 CK(run_fwd(g, s, 0, 0, true));
-                CKP(PC_LN, k_conf_tail_fwd<T>(c1, 2 * H, P + mp.conf_ln.w, P + mp.conf_ln.b, P + mp.conf3.w, P + mp.conf3.b, conf_logit, cf_mean, cf_rstd, B, 2 * H, cfg.ln_eps, s));
+                CKP(PC_LN, k_conf_tail_fwd<T>(c1, cw, P + mp.conf_ln.w, P + mp.conf_ln.b, P + mp.conf3.w, P + mp.conf3.b, conf_logit, cf_mean, cf_rstd, B, cw, cfg.ln_eps, s));
             }
         }
         if (pooled_out) CKP(PC_OTHER, k_to_f32<T>(pooled, H, pooled_out, H, B, H, s));
@@ -1206,6 +1260,12 @@ public:
         RGQA_REQUIRE(have_fwd, "get_conf: no forward pass recorded");
         return rgqa_check_hip(hipMemcpyAsync(out, conf_logit, sizeof(float) * B, hipMemcpyDeviceToDevice, s), "conf copy");
     }
+    int get_layer_proj(float* out, int ld, hipStream_t s) override {
+        RGQA_REQUIRE(layer_branch(), "get_layer_proj: this engine has no layer-wise confidence branch (rgqa_config.conf_branch = 2)");
+        RGQA_REQUIRE(have_fwd, "get_layer_proj: no forward pass recorded");
+        RGQA_REQUIRE(out != nullptr && ld >= conf_in(), "get_layer_proj: null buffer or row stride %d below x_layers * project_size = %d", ld, conf_in());
+        return k_to_f32<T>(projcat, conf_in(), out, ld, B, conf_in(), s);
+    }
     int backward2(const float* dl, int ldd, const float* dconf, int accumulate, hipStream_t s) override {
         RGQA_REQUIRE(have_fwd, "backward2: no forward pass recorded");
         RGQA_REQUIRE(G != nullptr, "backward2: no gradient arena bound");
@@ -1249,11 +1309,12 @@ public:
     // deferred group and its share of d(pooler pre-tanh) is added to gp1 (which backward_impl has just written) - ONE encoder backward follows;
     // otherwise (conf_only) the weight gradient is launched here and nothing flows on.
     int conf_backward(int accumulate, bool with_encoder, hipStream_t s) {
-        const int H = cfg.hidden;
-        CKP(PC_LN, k_conf_tail_bwd<TB>(dconf_dev, sv(c1), sv(c1dg), 2 * H, P + mp.conf_ln.w, P + mp.conf_ln.b, P + mp.conf3.w, cf_mean, cf_rstd, gc3, 2 * H,
-                                       G + mp.conf_ln.w, G + mp.conf_ln.b, G + mp.conf3.w, G + mp.conf3.b, accumulate, B, 2 * H, s));
+        const int H = cfg.hidden, cw = conf_width();
+        CKP(PC_LN, k_conf_tail_bwd<TB>(dconf_dev, sv(c1), sv(c1dg), cw, P + mp.conf_ln.w, P + mp.conf_ln.b, P + mp.conf3.w, cf_mean, cf_rstd, gc3, cw,
+                                       G + mp.conf_ln.w, G + mp.conf_ln.b, G + mp.conf3.w, G + mp.conf3.b, accumulate, B, cw, s));
         dconf_ready = false;
-        CKP(PC_OTHER, colsum_bias(gc3, 2 * H, mp.conf0, 0, 2 * H, B, accumulate, s));
+        CKP(PC_OTHER, colsum_bias(gc3, cw, mp.conf0, 0, cw, B, accumulate, s));
+        if (layer_branch()) return layer_backward(accumulate, with_encoder, s);
         GemmGroup g; gg_init(g);
         if (!with_encoder) {
             add_wgrad(g, gc3, 2 * H, mp.conf0, 0, 2 * H, sv(pooled), H, B, accumulate);
@@ -1264,11 +1325,39 @@ public:
         CKP(PC_OTHER, k_add_inplace<TB>(gp1, gcp, (size_t)B * H, s));
         return RGQA_OK;
     }
+    // The layer-wise branch below conf_fc.0's output gradient gc3 (conf_backward has written it and conf_fc.0's bias gradient): the gradient entering the
+    // projectors' tanh, the projectors' bias gradients, the X + 1 weight-gradient problems (wg_conf); with_encoder: also the gradient of every tap, complete on
+    // `s` before backward_encoder starts.
+    // The dgrads take the exact contraction length (add_dgrad's exact_k): the rounded-up one would read, behind slice i of a [B, X P] row, the next slice's values.
+    int layer_backward(int accumulate, bool with_encoder, hipStream_t s) {
+        const int H = cfg.hidden, X = cfg.x_layers, Pz = cfg.project_size, cin = conf_in(), cw = conf_width();
+        GemmGroup g; gg_init(g);
+        add_dgrad(g, gc3, cw, mp.conf0, 0, cw, dpc, cin, B, EPI_DTANH, sv(projcat), cin, true, true);
+        CK(run_dgrad(g, s, true));
+        for (int i = 0; i < X; ++i)
+            CKP(PC_OTHER, k_colsum<TB>(dpc + (size_t)i * Pz, cin, part, G + mp.projs[i].b, accumulate, B, Pz, s));
+        gg_init(wg_conf);
+        add_wgrad(wg_conf, gc3, cw, mp.conf0, 0, cw, sv(projcat), cin, B, accumulate);
+        for (int i = 0; i < X; ++i)
+            add_wgrad(wg_conf, dpc + (size_t)i * Pz, cin, mp.projs[i], 0, Pz, sv(taps) + (size_t)i * B * H, H, B, accumulate);
+        if (!with_encoder) { int r = run_wgrad(wg_conf, s); gg_init(wg_conf); return r; }
+        gg_init(g);
+        for (int i = 0; i < X; ++i)
+            add_dgrad(g, dpc + (size_t)i * Pz, cin, mp.projs[i], 0, Pz, dtap + (size_t)i * B * H, H, B, EPI_BIAS, nullptr, 0, true, true);
+        return run_dgrad(g, s, true);
+    }
+    // adds the gradient of tap `layer` to the [CLS] rows of `dy`, the gradient w.r.t. that layer's language output (compact: dy holds the B [CLS] rows alone)
+    int inject_tap(int layer, TB* dy, bool compact, hipStream_t s) {
+        const int H = cfg.hidden;
+        CKP(PC_OTHER, k_tap_inject<TB>(dtap + (size_t)layer * B * H, H, dy, H, compact ? nullptr : (fwd_varlen ? cu_dev : nullptr), compact ? 1 : Tn, B, H, s));
+        return RGQA_OK;
+    }
     // --freeze_vqa_branch (tasks/gqa_branched.py:80-83): only conf_fc is trained - the loss needs neither the answer head's nor the encoder's backward
+    bool taps_live = false;      // layer_backward has left dtap for the encoder backward that follows
     int backward_conf_only(int accumulate, hipStream_t s) {
         prof_block = PB_HEAD;
         CK(wait_bwd(s));
-        if (!accumulate) CK(rgqa_check_hip(hipMemsetAsync(G, 0, sizeof(float) * mp.conf0.w, s), "zero the gradients below conf_fc"));
+        if (!accumulate) CK(rgqa_check_hip(hipMemsetAsync(G, 0, sizeof(float) * (layer_branch() ? mp.projs[0].w : mp.conf0.w), s), "zero the gradients below the branch"));
         CK(conf_backward(accumulate, false, s));
         // every gradient segment is final on this stream: its event and its share of the clip norm, as after a full pass
         seg_cursor = 0;
@@ -1309,6 +1398,7 @@ public:
         if (cfg.conf_branch) {
             if (!dconf_ready) CK(rgqa_check_hip(hipMemsetAsync(dconf_dev, 0, sizeof(float) * B, s), "zero dconf"));      // an entry point that knows no dconf: zeros
             CK(conf_backward(accumulate, true, s));
+            taps_live = layer_branch();
         }
         return backward_encoder(accumulate, s);
     }
@@ -1326,7 +1416,7 @@ public:
         }
         CKP(PC_OTHER, k_cast_pad<TB>(dpooled, ld, gp2, H, B, H, 1.0f, s));
         CKP(PC_OTHER, k_dtanh_mul<TB>(gp2, sv(pooled), gp1, (size_t)B * H, s));
-        gg_init(wg_head);
+        gg_init(wg_head); gg_init(wg_conf);
         return backward_encoder(accumulate, s);
     }
 
@@ -1360,6 +1450,9 @@ public:
         CK(rgqa_check_hip(hipMemsetAsync(dyp[0], 0, (size_t)R * H * sizeof(TB), s), "zero dy"));
         gg_init(g); add_dgrad(g, gp1, H, mp.pooler, 0, H, gp2, H, B, EPI_BIAS, nullptr, 0); CK(run_dgrad(g, s, true));
         const bool tail = !stages.empty() && cls_tail(stages.back());
+        const bool inject = layer_branch() && taps_live;      // (backward_pooled: no gradient enters through the branch)
+        taps_live = false;
+        if (inject) CK(inject_tap(cfg.x_layers - 1, gp2, true, s));       // the last layer's tap: into the B [CLS] rows, before the scatter or the tail
         if (!tail) CKP(PC_OTHER, k_scatter_rows<TB>(gp2, H, dyp[0], H, cu, Tn, B, H, s));     // tail: the last FFN stage takes gp2 [B,H] as it is
         seg_cursor = 0;
         pend_n = 0; gg_init(wgm);      // (a backward pass that failed half-way leaves nothing behind)
@@ -1390,6 +1483,9 @@ public:
                 fin.begin(lnpart_s[par], LNPART_BLOCKS, H);     // LayerNorm-backward column sums: folded once per layer, with the layer's wgrad launch
             }
             TB* gz = gz_s[par][st.slot]; TB* gzd = gzd_s[par][st.slot]; TB* gqkv = gqkv_s[par][st.slot]; TB* gh = gh_s[par][st.slot];
+            // the FFN stage of cross-modality layer i < X - 1 is about to consume dyp[0], the gradient w.r.t. x<i>_lang: tap i's gradient joins its [CLS] rows in
+            // place (no pointer moves: the adjacency and swap bookkeeping below is untouched)
+            if (inject && st.kind == ST_FFN && si >= n_lr_stages && si != (int)stages.size() - 1) CK(inject_tap((si - n_lr_stages) / 3, dyp[0], false, s));
             const bool cross = st.kind == ST_ATT_CROSS;
             const bool shared_all = cross && st.active[1];
             auto rowp = [&](TB* base, int m, int width) { return base + (size_t)(m == 0 ? 0 : Rl) * width; };

@@ -210,6 +210,7 @@ template <typename T>
 int k_conf_tail_bwd(const float* dconf, const T* x, const T* dgelu, int ld, const float* gamma, const float* beta, const float* w3, const float* mean, const float* rstd,
                     T* gc, int ldg, float* dgamma, float* dbeta, float* dw3, float* db3, int accumulate, int B, int N, hipStream_t s);
 template <typename T> int k_add_inplace(T* a, const T* b, size_t n, hipStream_t s);
+#include "layer_taps.h"    // ---- layer_taps.hip: [CLS]-row taps of every cross-modality layer and their gradient injection (conf_branch = 2)
 
 // ---- resample.hip: the step of the soft resampling of the unanswerable questions (tasks/gqa_resampling.py:176-220): batch weights from the N weight
 // parameters, the row-weighted BCE head, and the closed-form gradient of the weight parameters with its SGD-momentum update

@@ -77,7 +77,7 @@ class Engine:
 
     def __init__(self, vocab_size=30522, hidden=768, heads=12, inter=3072, max_pos=512, type_vocab=2, l_layers=9,
                  x_layers=5, r_layers=5, feat_dim=2048, pos_dim=4, num_answers=1842, precision="bf16",
-                 ln_eps=1e-12, hidden_dropout=0.1, attn_dropout=0.1, arch=0, emb_dim=300, conf_branch=False):
+                 ln_eps=1e-12, hidden_dropout=0.1, attn_dropout=0.1, arch=0, emb_dim=300, conf_branch=False, project_size=128):
         self.lib = _lib.load()
         self.precision = precision
         # "bf16x3": split-f32 operands, three bf16 MFMA products per f32 product - the fast mode inside the reference's 1e-3 logits bound;
@@ -86,10 +86,19 @@ class Engine:
         precision = {"fp32": "f32", "x3": "bf16x3", "x3fwd": "bf16x3_fwd"}.get(precision, precision)
         self.precision = precision
         prec = {"bf16": PREC_BF16, "f32": PREC_F32, "bf16x3": PREC_BF16X3, "bf16x3_fwd": PREC_BF16X3_FWD}[precision]
+        if conf_branch == "layer" or conf_branch == 2:      # the C ABI's own value names the layer-wise branch too
+            conf_branch = "layer"
+        elif conf_branch not in (True, False, 0, 1, None):
+            raise ValueError("conf_branch must be False, True (the pooled-vector branch; 0 / 1) or \"layer\" (the layer-wise branch; 2); got %r" % (conf_branch,))
         self.cfg = Config(vocab_size, hidden, heads, inter, max_pos, type_vocab, l_layers, x_layers, r_layers, feat_dim,
-                          pos_dim, num_answers, prec, ln_eps, hidden_dropout, attn_dropout, arch, emb_dim, 1 if conf_branch else 0)
-        # conf_branch: the reference's GQAModel_branched (tasks/gqa_model_branched.py:14-51) - six conf_fc tensors behind logit_fc.3, `conf_logit` after forward
+                          pos_dim, num_answers, prec, ln_eps, hidden_dropout, attn_dropout, arch, emb_dim,
+                          2 if conf_branch == "layer" else (1 if conf_branch else 0), int(project_size))
+        # conf_branch: the reference's GQAModel_branched (tasks/gqa_model_branched.py:14-51) - six conf_fc tensors behind logit_fc.3, `conf_logit` after forward;
+        # "layer": its layer-wise sibling (tasks/gqa_branched_layer.py:280-320) - projs.<i>.proj.0 (Linear(H, project_size) -> Tanh on the [CLS] row of every
+        # cross-modality layer) in front of a conf_fc that reads the x_layers projections side by side; `layer_proj` after forward
         self.conf_branch = bool(conf_branch)
+        self.layer_branch = conf_branch == "layer"
+        self.project_size = int(project_size) if self.layer_branch else None
         h = C.c_void_p()
         check(self.lib.rgqa_engine_create(C.byref(self.cfg), C.byref(h)))
         self.h = h
@@ -380,6 +389,16 @@ class Engine:
         check(self.lib.rgqa_engine_backward_conf(self.h, ptr(dconf), 1 if accumulate else 0, _stream()))
         self._wev_refs.pop("bwd", None)
         self._seg_sumsq_valid = self._seg_sumsq is not None
+
+    @property
+    def layer_proj(self):
+        """[B, x_layers * project_size] f32 copy of the projections the layer-wise branch fed to conf_fc in the last forward (tanh outputs; column block i belongs
+        to cross-modality layer i); Engine(conf_branch="layer") only"""
+        if not self.layer_branch:
+            raise RuntimeError("layer_proj: this engine has no layer-wise confidence branch (Engine(conf_branch=\"layer\"))")
+        out = torch.empty(self.shape[0], self.cfg.x_layers * self.cfg.project_size, dtype=torch.float32, device=self.device)
+        check(self.lib.rgqa_engine_get_layer_proj(self.h, ptr(out), out.stride(0), _stream()))
+        return out
 
     @property
     def conf_logit(self):

@@ -284,10 +284,11 @@ class ArenaBinding(object):
         return self.respect_frozen and not p.requires_grad
 
     def conf_only(self):
-        """the reference's --freeze_vqa_branch state: every parameter outside conf_fc frozen, every conf_fc parameter trained"""
+        """the reference's --freeze_vqa_branch state: every parameter outside conf_fc (and, in the layer-wise model, projs: tasks/gqa_branched_layer.py:348-352)
+        frozen, every parameter of the branch trained"""
         if not self.respect_frozen:
             return False
-        return all(p.requires_grad == sp.name.startswith("conf") for sp, p in self.params)
+        return all(p.requires_grad == sp.name.startswith(("conf_fc.", "projs.")) for sp, p in self.params)
 
     def _views(self):
         """the gradient-arena view of every live parameter, made once per gradient arena: re-attaching them after the trainer's
@@ -549,6 +550,7 @@ class LXRTFeatureExtraction(BertPreTrainedModel):
         self.precision = precision or os.environ.get("RGQA_PRECISION", "bf16")
         self.__dict__["_head"] = None          # not a registered submodule: the head belongs to GQAModel's state_dict
         self.__dict__["_conf_head"] = None     # ... and conf_fc to GQAModel_branched's
+        self.__dict__["_projs"] = None         # ... and projs to the layer-wise GQAModel_branched's (tasks/gqa_branched_layer.py)
         self._binding = ArenaBinding()
         self._fwd_counter = 0
         self._seed_base = None
@@ -568,11 +570,14 @@ class LXRTFeatureExtraction(BertPreTrainedModel):
     # -- engine / arena -------------------------------------------------------------------------------------------
     def _make_engine(self, num_answers):
         c = self.config
+        projs = self.__dict__.get("_projs")
         self._binding.engine = Engine(vocab_size=c.vocab_size, hidden=c.hidden_size, heads=c.num_attention_heads,
                                       inter=c.intermediate_size, max_pos=c.max_position_embeddings, type_vocab=c.type_vocab_size,
                                       l_layers=VISUAL_CONFIG.l_layers, x_layers=VISUAL_CONFIG.x_layers, r_layers=VISUAL_CONFIG.r_layers,
                                       feat_dim=VISUAL_CONFIG.visual_feat_dim, pos_dim=VISUAL_CONFIG.visual_pos_dim,
-                                      num_answers=num_answers, precision=self.precision, conf_branch=self.__dict__.get("_conf_head") is not None,
+                                      num_answers=num_answers, precision=self.precision,
+                                      conf_branch="layer" if projs is not None else self.__dict__.get("_conf_head") is not None,
+                                      project_size=projs[0].proj[0].out_features if projs is not None else 128,
                                       hidden_dropout=c.hidden_dropout_prob, attn_dropout=c.attention_probs_dropout_prob)
 
     def _named_for_binding(self):
@@ -581,6 +586,8 @@ class LXRTFeatureExtraction(BertPreTrainedModel):
             named.update({"logit_fc." + k: v for k, v in self._head.named_parameters()})
             if self._conf_head is not None:
                 named.update({"conf_fc." + k: v for k, v in self._conf_head.named_parameters()})
+            if self._projs is not None:
+                named.update({"projs." + k: v for k, v in self._projs.named_parameters()})
         else:
             # encoder-only use: the engine still owns an (unused) head; keep its slices as hidden zero parameters
             e = self._binding.engine
@@ -593,17 +600,28 @@ class LXRTFeatureExtraction(BertPreTrainedModel):
     def _rebind(self):
         self._binding.bind(self._binding.engine, self._named_for_binding())
 
-    def attach_head(self, logit_fc, conf_fc=None):
+    def attach_head(self, logit_fc, conf_fc=None, projs=None):
         """Fuses a GQA answer head (nn.Sequential(Linear, GeLU, LayerNorm, Linear), tasks/gqa_model.py:22-27) into the engine; conf_fc: also the
-        confidence branch of the branched model (the same Sequential with one output, tasks/gqa_model_branched.py:28-33)."""
+        confidence branch of the branched model (the same Sequential with one output, tasks/gqa_model_branched.py:28-33); projs (with conf_fc): the
+        layer-wise branch - a ModuleList of one GQAProjector (`.proj` = Linear(H, P) -> Tanh) per cross-modality layer in front of a conf_fc of input
+        width x_layers * P (tasks/gqa_branched_layer.py:47-59, :280-291)."""
         lin0, lin3 = logit_fc[0], logit_fc[3]
         H = self.config.hidden_size
+        if projs is not None:
+            X = VISUAL_CONFIG.x_layers
+            ok = conf_fc is not None and len(projs) == X and X >= 1 and all(
+                isinstance(getattr(m, "proj", None), nn.Sequential) and isinstance(m.proj[0], nn.Linear) and isinstance(m.proj[1], nn.Tanh) and m.proj[0].in_features == H
+                and m.proj[0].out_features == projs[0].proj[0].out_features for m in projs)
+            if not ok:
+                raise ValueError("attach_head expects projs = x_layers modules with .proj = Linear(H, P) -> Tanh, and a conf_fc")
         if conf_fc is not None:
             c0, c3 = conf_fc[0], conf_fc[3]
-            if not (isinstance(c0, nn.Linear) and isinstance(c3, nn.Linear) and isinstance(conf_fc[2], nn.LayerNorm) and c0.in_features == H
-                    and c0.out_features == 2 * H and c3.in_features == 2 * H and c3.out_features == 1):
-                raise ValueError("attach_head expects conf_fc = Linear(H,2H) -> GeLU -> LayerNorm(2H) -> Linear(2H,1)")
+            cin = H if projs is None else len(projs) * projs[0].proj[0].out_features
+            if not (isinstance(c0, nn.Linear) and isinstance(c3, nn.Linear) and isinstance(conf_fc[2], nn.LayerNorm) and c0.in_features == cin
+                    and c0.out_features == 2 * cin and c3.in_features == 2 * cin and c3.out_features == 1):
+                raise ValueError("attach_head expects conf_fc = Linear(n,2n) -> GeLU -> LayerNorm(2n) -> Linear(2n,1) with n = H (n = x_layers * P with projs)")
         self.__dict__["_conf_head"] = conf_fc
+        self.__dict__["_projs"] = projs
         self._binding.respect_frozen = conf_fc is not None
         if not (isinstance(lin0, nn.Linear) and isinstance(lin3, nn.Linear) and isinstance(logit_fc[2], nn.LayerNorm)
                 and lin0.in_features == H and lin0.out_features == 2 * H and lin3.in_features == 2 * H):

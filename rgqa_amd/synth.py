@@ -136,6 +136,18 @@ def branched_target():
     return t
 
 
+# The layer-wise confidence-branch fixture (tests/golden/g16_branched_layer.npz, tools/gen_g16_branched_layer.py): the small config with three cross-modality
+# layers, 16 projected values per layer, small_batch(8) under branched_target()
+LAYER_SMALL = dict(SMALL, x_layers=3)
+LAYER_PROJECT_SIZE = 16
+
+
+def layer_branched_fill(shapes):
+    """The fixture's weights: the deterministic filler as it is.  It already meets the two conditions the generator asserts (max |projcat| = 0.37 - no tanh is
+    saturated; every group of layers feels the confidence loss at more than 100 times the f32 gate of the GPU tests), so the branch's weights are not scaled."""
+    return fill_state_dict(shapes)
+
+
 def full_batch(T):
     b = synth_batch(4, T, seed=4242 + T)
     ids = b["input_ids"]
