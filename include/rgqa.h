@@ -130,7 +130,8 @@ int rgqa_engine_workspace_bytes(rgqa_engine* e, int B, int T, int O, size_t* out
 /* params / grads: f32 arenas of arena_elems; params_lp / params_lp_t: the operand copies of the linear weights and their
  * transposes at the same element offsets - bf16 arenas of arena_elems in bf16 precision, 4-byte-per-element split-f32 arenas
  * (128-byte aligned) in bf16x3 precision, may be null in f32 precision; workspace: ws_bytes of scratch.  Must be called again
- * when B, T or O change. */
+ * when B, T or O change.  T, O <= 64; arch 2 (UNITER, one sequence of T + O rows per sample): T + O <= 64.  A refused call launches nothing and leaves
+ * the engine unbound: bind again before the next pass. */
 int rgqa_engine_bind(rgqa_engine* e, float* params, float* grads, void* params_lp, void* params_lp_t,
                      void* workspace, size_t ws_bytes, int B, int T, int O);
 /* refresh the low-precision weight copies from the f32 master arena (after load_state_dict / external updates) */

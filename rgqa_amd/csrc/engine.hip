@@ -701,8 +701,10 @@ public:
     }
 
     int bind(float* p, float* g, void* plp, void* plpt, void* w, size_t wb, int B_, int T_, int O_) override {
+        ws = nullptr; have_fwd = false;      // a refused bind leaves the engine unbound (the dry plan of workspace_bytes may already describe the refused shape)
         RGQA_REQUIRE(p != nullptr && w != nullptr, "bind: null parameter arena or workspace");
         RGQA_REQUIRE(B_ > 0 && T_ > 0 && O_ > 0 && T_ <= 64 && O_ <= 64, "bind: B=%d T=%d O=%d unsupported (T, O <= 64)", B_, T_, O_);
+        if (joint) RGQA_REQUIRE(T_ + O_ <= 64, "bind: T + O = %d + %d = %d unsupported (UNITER: one sequence of T + O <= 64 rows per sample)", T_, O_, T_ + O_);
         RGQA_REQUIRE(T_ <= cfg.max_pos, "bind: T=%d exceeds max_position_embeddings=%d", T_, cfg.max_pos);
         if (LP) RGQA_REQUIRE(plp != nullptr && plpt != nullptr, "bind: bf16 / bf16x3 precision needs the operand-copy arenas");
         if (X3) RGQA_REQUIRE(((uintptr_t)plp % 128) == 0 && ((uintptr_t)plpt % 128) == 0, "bind: the split-f32 arenas must be 128-byte aligned");      // (MIXED: the transposed copy is bf16; the same alignment costs nothing)

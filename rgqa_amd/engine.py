@@ -200,6 +200,7 @@ class Engine:
         owner = self._sharded_owner
         if owner is not None and hasattr(owner, "_join_gather"):
             owner._join_gather()
+        self.shape = None       # (a refused bind leaves the engine planned for no shape: the next call binds again)
         need = C.c_size_t()
         check(self.lib.rgqa_engine_workspace_bytes(self.h, B, T, O, C.byref(need)))
         if self.workspace is None or self.workspace.numel() < need.value:
