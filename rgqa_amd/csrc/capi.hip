@@ -5,7 +5,6 @@
 
 struct rgqa_engine { EngineBase* impl; };
 EngineBase* make_butd_engine(const rgqa_config& cfg);
-int launch_gemm_nt256_probe(GemmGroup& g, int mt, hipStream_t s);      // gemm_mfma256.hip
 
 #define S(x) reinterpret_cast<hipStream_t>(x)
 #define NEED(e) do { if ((e) == nullptr || (e)->impl == nullptr) { rgqa_set_error("null engine handle"); return RGQA_ERR_ARG; } } while (0)
@@ -22,7 +21,6 @@ extern int g_rgqa_cls_tail;
 extern int g_rgqa_attn_pair;
 extern int g_rgqa_skip_wgrad;
 extern int g_rgqa_wgrad_merge;
-extern int g_rgqa_nt_splitk;
 extern int g_rgqa_nt_panel;
 extern int g_rgqa_wgrad_sets;
 extern int g_rgqa_dgrad_nn;

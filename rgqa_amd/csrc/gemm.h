@@ -1,4 +1,4 @@
-// Grouped GEMM descriptors + the shared epilogue (used by the bf16 MFMA kernels and the f32 kernel).
+// Grouped GEMM descriptors, the element-wise epilogue (128 x 128 MFMA kernels, f32 kernel, split-K finish) and every host launcher's declaration.
 #pragma once
 #include "common.h"
 
@@ -60,7 +60,7 @@ struct GemmGroupT {
                         // stagger / 16 x (its K-step count) x ~2 us - inside the slack it has anyway - so that its K loops run while the others store their tiles
     const void* zeros;  // TN LDS-DMA kernel: >= 16 zero bytes on the device (source of the contraction tail's A rows)
     unsigned long long* stamps;   // clock probe only (rgqa_probe_gemm: separately instantiated, stamped kernels): 8 words per block
-    float* splitk_ws;   // bf16 NT launches: scratch for the split-K path of skinny problems (gemm_mfma256.hip), splitk_floats floats, or null
+    float* splitk_ws;   // NT launches, bf16 or split-f32 operands: scratch for the split-K path of skinny problems (gemm_nt256.h), splitk_floats floats, or null
     size_t splitk_floats;
     DropCfg drop;
     GemmProblem p[NP];
@@ -69,17 +69,20 @@ using GemmGroup = GemmGroupT<GEMM_MAX_PROBLEMS>;
 using GemmGroupNT = GemmGroupT<GEMM_NT_MAX_PROBLEMS>;
 static inline const GemmGroupNT& nt_prefix(const GemmGroup& g) { return reinterpret_cast<const GemmGroupNT&>(g); }
 
-// Epilogue on 4 consecutive columns n0..n0+3 of row m. OutT = float or bf16_t; AuxT = act type.
-template <typename OutT, typename AuxT>
-__device__ __forceinline__ void gemm_epilogue4_e(const GemmProblem& P, const int epi, const DropCfg& drop, int m, int n0, float v[4]) {
-    if (m >= P.M || n0 >= P.N) return;
-    const int nvalid = (P.N - n0) >= 4 ? 4 : (P.N - n0);
-    if (P.bias != nullptr) {
+// bijective XCD-aware remap of a block id (blocks b and b + 8 share an XCD): consecutive tile ids run on one XCD / L2
+__device__ __forceinline__ int xcd_remap256(int b, int nwg) {
+    int q = nwg >> 3, r = nwg & 7, xcd = b & 7;
+    return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (b >> 3);
+}
+
+__host__ __device__ __forceinline__ bool epi_needs_aux(int epi) { return epi == EPI_RESID_DROP || epi == EPI_DGELU || epi == EPI_ADD || epi == EPI_DTANH || epi == EPI_DRELU_DROP; }
+
+// ---- the element-wise epilogue ladder, once: activation / dropout / aux arithmetic on the 4 consecutive columns n0..n0+3 of row m.
+// v = acc + bias on entry, the result on exit; a = the aux operand (read only where epi_needs_aux); pre = the second output (gelu' for EPI_GELU,
+// else acc + bias).  m, n0 are GLOBAL indices of the problem: they address the dropout stream.  EPI_ACCUM leaves v as it is: epi_accum4 follows.
+__device__ __forceinline__ void epi_ladder4(const GemmProblem& P, const int epi, const DropCfg& drop, int m, int n0, const float a[4], float v[4], float pre[4]) {
 #pragma unroll
-        for (int i = 0; i < 4; ++i) if (i < nvalid) v[i] += P.bias[n0 + i];
-    }
-    OutT* crow = reinterpret_cast<OutT*>(P.C) + (size_t)m * P.ldc + n0;
-    float pre[4] = {v[0], v[1], v[2], v[3]};
+    for (int i = 0; i < 4; ++i) pre[i] = v[i];
     if (epi == EPI_GELU) {
 #pragma unroll
         for (int i = 0; i < 4; ++i) { v[i] = gelu_f(pre[i]); pre[i] = dgelu_f(pre[i]); }
@@ -93,37 +96,54 @@ __device__ __forceinline__ void gemm_epilogue4_e(const GemmProblem& P, const int
             v[i] = fmaxf(pre[i], 0.f);
             if (epi == EPI_RELU_DROP) v[i] = drop_apply(d, (uint32_t)m * (uint32_t)P.N + (uint32_t)(n0 + i), v[i]);
         }
-    } else if (epi == EPI_RESID_DROP || epi == EPI_DGELU || epi == EPI_ADD || epi == EPI_DTANH || epi == EPI_DRELU_DROP) {
+    } else if (epi == EPI_DRELU_DROP) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) v[i] = a[i] > 0.f ? v[i] * drop.scale : 0.f;
+    } else if (epi == EPI_RESID_DROP) {
+        DropCfg d = drop; d.seed_hi ^= P.drop_site;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) v[i] = drop_apply(d, (uint32_t)m * (uint32_t)P.N + (uint32_t)(n0 + i), v[i]) + a[i];
+    } else if (epi == EPI_DGELU) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) v[i] = v[i] * a[i];
+    } else if (epi == EPI_DTANH) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) v[i] = v[i] * (1.0f - a[i] * a[i]);
+    } else if (epi == EPI_ADD) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) v[i] = v[i] + a[i];
+    }
+}
+// EPI_ACCUM: C[m, n0 .. n0 + nvalid) += v  (C is f32)
+__device__ __forceinline__ void epi_accum4(const GemmProblem& P, int m, int n0, int nvalid, const float v[4]) {
+    float* c = reinterpret_cast<float*>(P.C) + (size_t)m * P.ldc + n0;
+    if (nvalid == 4) {
+        float o[4]; load4(c, o);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) o[i] += v[i];
+        store4(c, o);
+    } else for (int i = 0; i < nvalid; ++i) c[i] += v[i];
+}
+
+// Epilogue on 4 consecutive columns n0..n0+3 of row m, operands fetched at use. OutT = float, bf16_t or sf32; AuxT = act type.
+template <typename OutT, typename AuxT>
+__device__ __forceinline__ void gemm_epilogue4_e(const GemmProblem& P, const int epi, const DropCfg& drop, int m, int n0, float v[4]) {
+    if (m >= P.M || n0 >= P.N) return;
+    const int nvalid = (P.N - n0) >= 4 ? 4 : (P.N - n0);
+    if (P.bias != nullptr) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) if (i < nvalid) v[i] += P.bias[n0 + i];
+    }
+    float a[4] = {0.f, 0.f, 0.f, 0.f};
+    if (epi_needs_aux(epi)) {
         const AuxT* arow = reinterpret_cast<const AuxT*>(P.aux) + (size_t)m * P.ldaux + n0;
-        float a[4] = {0.f, 0.f, 0.f, 0.f};
         if (nvalid == 4) load4(arow, a);
         else for (int i = 0; i < nvalid; ++i) a[i] = ld_elem(arow + i);
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            if (epi == EPI_RESID_DROP) {
-                uint32_t idx = (uint32_t)m * (uint32_t)P.N + (uint32_t)(n0 + i);
-                DropCfg d = drop; d.seed_hi ^= P.drop_site;
-                v[i] = drop_apply(d, idx, v[i]) + a[i];
-            } else if (epi == EPI_DGELU) {
-                v[i] = v[i] * a[i];
-            } else if (epi == EPI_DTANH) {
-                v[i] = v[i] * (1.0f - a[i] * a[i]);
-            } else if (epi == EPI_DRELU_DROP) {
-                v[i] = a[i] > 0.f ? v[i] * drop.scale : 0.f;
-            } else {
-                v[i] = v[i] + a[i];
-            }
-        }
-    } else if (epi == EPI_ACCUM) {
-        float* c = reinterpret_cast<float*>(P.C) + (size_t)m * P.ldc + n0;
-        if (nvalid == 4) {
-            float o[4]; load4(c, o);
-#pragma unroll
-            for (int i = 0; i < 4; ++i) o[i] += v[i];
-            store4(c, o);
-        } else for (int i = 0; i < nvalid; ++i) c[i] += v[i];
-        return;
     }
+    float pre[4];
+    epi_ladder4(P, epi, drop, m, n0, a, v, pre);
+    if (epi == EPI_ACCUM) { epi_accum4(P, m, n0, nvalid, v); return; }
+    OutT* crow = reinterpret_cast<OutT*>(P.C) + (size_t)m * P.ldc + n0;
     if (nvalid == 4) {
         store4(crow, v);
         if (P.Cb != nullptr) store4(reinterpret_cast<bf16_t*>(P.Cb) + (size_t)m * P.ldc + n0, v);      // split-f32 results (bf16x3_fwd): the bf16 image beside them
@@ -147,8 +167,6 @@ __device__ __forceinline__ void gemm_epilogue4(const GemmProblem& P, const DropC
 // ---- two-phase epilogue for the MFMA kernels: all bias / aux operands of a lane are fetched up front (one exposed
 // memory round trip) instead of one dependent load per 4 outputs (loads cannot be hoisted over the stores in between).
 struct Aux4 { float a[4]; };
-
-__host__ __device__ __forceinline__ bool epi_needs_aux(int epi) { return epi == EPI_RESID_DROP || epi == EPI_DGELU || epi == EPI_ADD || epi == EPI_DTANH || epi == EPI_DRELU_DROP; }
 
 __device__ __forceinline__ void epi_fetch_bias(const GemmProblem& P, int n0, float b[4]) {
     b[0] = b[1] = b[2] = b[3] = 0.f;
@@ -185,46 +203,9 @@ __device__ __forceinline__ void epi_finish(const GemmProblem& P, const int epi, 
     const int nvalid = (P.N - n0) >= 4 ? 4 : (P.N - n0);
 #pragma unroll
     for (int i = 0; i < 4; ++i) v[i] += b[i];
-    float pre[4] = {v[0], v[1], v[2], v[3]};
-    if (epi == EPI_GELU) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) { v[i] = gelu_f(pre[i]); pre[i] = dgelu_f(pre[i]); }
-    } else if (epi == EPI_TANH) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) v[i] = tanhf(pre[i]);
-    } else if (epi == EPI_RELU || epi == EPI_RELU_DROP) {
-        DropCfg d = drop; d.seed_hi ^= P.drop_site;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            v[i] = fmaxf(pre[i], 0.f);
-            if (epi == EPI_RELU_DROP) v[i] = drop_apply(d, (uint32_t)m * (uint32_t)P.N + (uint32_t)(n0 + i), v[i]);
-        }
-    } else if (epi == EPI_DRELU_DROP) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) v[i] = a[i] > 0.f ? v[i] * drop.scale : 0.f;
-    } else if (epi == EPI_RESID_DROP) {
-        DropCfg d = drop; d.seed_hi ^= P.drop_site;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) v[i] = drop_apply(d, (uint32_t)m * (uint32_t)P.N + (uint32_t)(n0 + i), v[i]) + a[i];
-    } else if (epi == EPI_DGELU) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) v[i] = v[i] * a[i];
-    } else if (epi == EPI_DTANH) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) v[i] = v[i] * (1.0f - a[i] * a[i]);
-    } else if (epi == EPI_ADD) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) v[i] = v[i] + a[i];
-    } else if (epi == EPI_ACCUM) {
-        float* c = reinterpret_cast<float*>(P.C) + (size_t)m * P.ldc + n0;
-        if (nvalid == 4) {
-            float o[4]; load4(c, o);
-#pragma unroll
-            for (int i = 0; i < 4; ++i) o[i] += v[i];
-            store4(c, o);
-        } else for (int i = 0; i < nvalid; ++i) c[i] += v[i];
-        return;
-    }
+    float pre[4];
+    epi_ladder4(P, epi, drop, m, n0, a, v, pre);
+    if (epi == EPI_ACCUM) { epi_accum4(P, m, n0, nvalid, v); return; }
     OutT* crow = reinterpret_cast<OutT*>(P.C) + (size_t)m * P.ldc + n0;
     if (nvalid == 4) {
         store4(crow, v);
@@ -237,12 +218,24 @@ __device__ __forceinline__ void epi_finish(const GemmProblem& P, const int epi, 
     }
 }
 
-// host launchers (gemm_mfma.hip / gemm_f32.hip). out_f32: C is float (else bf16). All return RGQA_* codes.
+// ---- host launchers.  out_f32: C is float (else the act type).  All return RGQA_* codes.
+// bf16 entries (gemm_mfma.hip): the LDS-DMA kernels where the group is eligible, else the 128 x 128 register-staged kernels
 int launch_gemm_nt_bf16(GemmGroup& g, int out_f32, hipStream_t s);
 int launch_gemm_tn_bf16(GemmGroup& g, int out_f32, hipStream_t s);
+// bf16 LDS-DMA kernels (gemm_mfma256.hip), behind the two entries above
+bool gemm_nt256_eligible(const GemmGroup& g, int out_f32);
+int launch_gemm_nt256_any(GemmGroup& g, int out_f32, hipStream_t s);       // split-K for skinny single problems, else one of the next two
+int launch_gemm_nt256_bf16(GemmGroup& g, hipStream_t s);
+int launch_gemm_nt256_f32out(GemmGroup& g, hipStream_t s);
+int launch_gemm_nt256_probe(GemmGroup& g, int mt, hipStream_t s);          // stamped instantiations (rgqa_probe_gemm)
+bool gemm_tn_dma_eligible(const GemmGroup& g);
+int launch_gemm_tn_dma_bf16(GemmGroup& g, hipStream_t s);
 // bf16x3 precision (gemm_x3.hip): A / B (and C, aux unless out_f32) in the split-f32 layout
 int launch_gemm_nt_x3(GemmGroup& g, int out_f32, hipStream_t s);
 int launch_gemm_tn_x3(GemmGroup& g, hipStream_t s);
-// f32 generic: A(m,k) = A[m*sam + k*sak], B(k,n) = B[k*sbk + n*sbn]; everything f32.
+// f32 generic (gemm_f32.hip): A(m,k) = A[m*sam + k*sak], B(k,n) = B[k*sbk + n*sbn]; everything f32.
 int launch_gemm_f32(GemmGroup& g, int trans_a, int trans_b, hipStream_t s);
+// shared host pieces (gemm_mfma.hip, gemm_mfma256.hip)
 void gemm_group_finalize(GemmGroup& g, int bm, int bn);
+int gemm_tn_prepare(GemmGroup& g, int bm, int bn);      // LDS-DMA wgrad launches: longest contraction first, g.zeros, tile numbering
+extern int g_rgqa_nt_splitk;      // rgqa_debug_set key 7 (gemm_mfma256.hip): 0 = skinny NT problems stay whole, in either operand precision

@@ -1,5 +1,5 @@
 // Device helpers shared by the LDS-DMA GEMM kernels (gemm_nt256.h, gemm_mfma256.hip, gemm_x3.hip): LDS-DMA issue, the swizzled
-// operand image, the XCD-aware tile map and the common epilogue.
+// operand image, the common NT epilogue and the frame of the weight-gradient (TN) kernels: block id -> tile, output-tile store.
 #pragma once
 #include <type_traits>
 #include "gemm.h"
@@ -31,10 +31,6 @@ __device__ __forceinline__ unsigned lds_addr(const void* p) {
     return (unsigned)(uintptr_t)(__attribute__((address_space(3))) const unsigned char*)(p);
 }
 
-__device__ __forceinline__ int xcd_remap256(int b, int nwg) {
-    int q = nwg >> 3, r = nwg & 7, xcd = b & 7;
-    return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (b >> 3);
-}
 // LDS image of a [rows][64] bf16 operand tile: 128-B rows, 16-B chunk c of row r at r*128 + ((c ^ ((r>>1)&7))<<4).
 // A ds_read_b128 is served per 16-lane group = 16 consecutive rows at one logical chunk: bank slot (mod 256 B) is
 // (r&1)*8 + (c ^ ((r>>1)&7)) - 16 distinct slots, conflict-free.  (c ^ (r&7), used first, repeats every 8 rows at equal
@@ -308,3 +304,74 @@ __device__ __forceinline__ bf16x8 tr_frag_dma(const unsigned char* tile, int r0,
     r[4] = hi[0]; r[5] = hi[1]; r[6] = hi[2]; r[7] = hi[3];
     return r;
 }
+
+// ---- frame of the LDS-DMA weight-gradient (TN) kernels (gemm_tn_dma_kernel in gemm_mfma256.hip, gemm_tn_x3_kernel in gemm_x3.hip): 8 waves (2 x 4), output
+// tile TM_ROWS x 256, a lane's accumulators acc[tm][tn] = 4 consecutive columns of one row (MFMA roles swapped as in the NT kernels).
+// The two pieces are MACROS that name everything they read or declare, not functions: as __forceinline__ functions (references or a struct returned by
+// value) they reach the optimiser in another shape and hipcc then builds another kernel around the same K loop - gemm_tn_dma_kernel<0, 4> 4,500 -> 3,456
+// instructions and 194 -> 190 VGPRs with the store as a function, another scalar prologue with the tile map as one - while the text below, expanded in place,
+// gives both kernels' parent streams instruction for instruction (profiles/gemm_family_isa_diff.md).  These kernels are the step time: their stream stays.
+#define WN 256
+// Block id -> tile.  The launcher sorts the problems by contraction length; problems of equal length form a class, and the ids of a class
+// are re-dealt so that the blocks of one XCD (equal id mod 8, dispatched in id order) walk ONE contiguous run of the class's tile list:
+// a run is a compact piece of one weight matrix - M-tiles of one N-tile first - whose tiles stream the same operand rows at the same time
+// through that XCD's L2.  (Per problem instead of per class, the runs were 3-5 tiles: L2 hit rate 0.39.)  Every XCD gets an eighth of
+// every class, so the XCDs stay balanced whatever the mix of lengths.
+// Declares P (the problem), local (the tile's m-major id inside it) and m0, n0 (its origin); also tile0, p0, K0, c_lo, c_hi, tile, pi, tiles_m, tix.
+#define TN_TILE_MAP(g, TM_ROWS, P, local, m0, n0)                                                     \
+    const int tile0 = blockIdx.x;                                                                     \
+    int p0 = 0;                                                                                       \
+_Pragma("unroll")                                                                                     \
+    for (int i = 1; i < GEMM_MAX_PROBLEMS; ++i)                                                       \
+        if (i < (g).count && tile0 >= (g).p[i].tile_start) p0 = i;                                    \
+    const int K0 = (g).p[p0].K;                                                                       \
+    int c_lo = (g).p[p0].tile_start, c_hi = (g).total_tiles;                                          \
+_Pragma("unroll")                                                                                     \
+    for (int i = 0; i < GEMM_MAX_PROBLEMS; ++i)                                                       \
+        if (i < (g).count) {                                                                          \
+            if ((g).p[i].K == K0) c_lo = min(c_lo, (g).p[i].tile_start);                              \
+            else if ((g).p[i].K < K0) c_hi = min(c_hi, (g).p[i].tile_start);                          \
+        }                                                                                             \
+    const int tile = c_lo + xcd_remap256(tile0 - c_lo, c_hi - c_lo);                                  \
+    int pi = 0;                                                                                       \
+_Pragma("unroll")                                                                                     \
+    for (int i = 1; i < GEMM_MAX_PROBLEMS; ++i)                                                       \
+        if (i < (g).count && tile >= (g).p[i].tile_start) pi = i;                                     \
+    const GemmProblem& P = (g).p[pi];                                                                 \
+    const int tiles_m = cdiv(P.M, TM_ROWS);                                                           \
+    const int tix = tile - P.tile_start;                                                              \
+    const int local = (tix % tiles_m) * P.tiles_n + (tix / tiles_m);     /* back to the m-major id */ \
+    const int m0 = (local / P.tiles_n) * (TM_ROWS), n0 = (local % P.tiles_n) * WN;
+// The bias gradient's column sums (do_cs: wave-uniform) and the wave's 16*MTW x 64 piece of the f32 output tile, stored or accumulated (ACCUM), guarded at the
+// edges.  Last statement of a kernel: declares Cc, cs_out, ldc, accum, fr, fq.
+#define TN_STORE_TILE(ACCUM, MTW, P, do_cs, lane, wm, wn, m0, n0, acc, cs)                                          \
+    float* Cc = reinterpret_cast<float*>((P).C);                                                                    \
+    float* cs_out = (P).colsum_out;                                                                                 \
+    const int ldc = (P).ldc;                                                                                        \
+    constexpr bool accum = (ACCUM) != 0;                                                                            \
+    if ((do_cs) && (lane >> 4) == 0) {                                                                              \
+_Pragma("unroll")                                                                                                   \
+        for (int tm = 0; tm < (MTW); ++tm) {                                                                        \
+            const int m = (m0) + (wm) * (16 * (MTW)) + tm * 16 + (lane & 15);                                       \
+            if (m < (P).M) cs_out[m] = accum ? cs_out[m] + (cs)[tm][0] : (cs)[tm][0];                               \
+        }                                                                                                           \
+    }                                                                                                               \
+    const int fr = lane & 15, fq = lane >> 4;                                                                       \
+_Pragma("unroll")                                                                                                   \
+    for (int tm = 0; tm < (MTW); ++tm) {                                                                            \
+        const int m = (m0) + (wm) * (16 * (MTW)) + tm * 16 + fr;                                                    \
+_Pragma("unroll")                                                                                                   \
+        for (int tn = 0; tn < 4; ++tn) {                                                                            \
+            const int n = (n0) + (wn) * 64 + tn * 16 + 4 * fq;                                                      \
+            if (m < (P).M && n < (P).N) {                                                                           \
+                float* c = Cc + (size_t)m * ldc + n;                                                                \
+                float v[4] = {(acc)[tm][tn][0], (acc)[tm][tn][1], (acc)[tm][tn][2], (acc)[tm][tn][3]};              \
+                if (n + 3 < (P).N) {                                                                                \
+                    if (accum) { float o[4]; load4(c, o); v[0] += o[0]; v[1] += o[1]; v[2] += o[2]; v[3] += o[3]; } \
+                    store4(c, v);                                                                                   \
+                } else {                                                                                            \
+                    for (int i = 0; i < (P).N - n; ++i) c[i] = accum ? c[i] + v[i] : v[i];                          \
+                }                                                                                                   \
+            }                                                                                                       \
+        }                                                                                                           \
+    }

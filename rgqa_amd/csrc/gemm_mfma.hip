@@ -17,12 +17,6 @@
 
 typedef __attribute__((address_space(3))) bf16x4 lds_bf16x4;
 
-__device__ __forceinline__ int xcd_remap(int b, int nwg) {
-    // bijective XCD-aware remap (blocks b and b+8 share an XCD): consecutive tile ids run on one XCD/L2
-    int q = nwg >> 3, r = nwg & 7, xcd = b & 7;
-    return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (b >> 3);
-}
-
 __device__ __forceinline__ const GemmProblem& find_problem(const GemmGroup& g, int tile, int& local) {
     int pi = 0;
 #pragma unroll
@@ -54,7 +48,7 @@ __global__ __launch_bounds__(NTHREADS) void gemm_nt_kernel(const GemmGroup g) {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int wm = wave >> 1, wn = wave & 1;
     int local;
-    const GemmProblem& P = find_problem(g, xcd_remap(blockIdx.x, g.total_tiles), local);
+    const GemmProblem& P = find_problem(g, xcd_remap256(blockIdx.x, g.total_tiles), local);
     const int m0 = (local / P.tiles_n) * BM, n0 = (local % P.tiles_n) * BN;
     const int K = P.K, nkt = (K + BK - 1) / BK;
 
@@ -165,7 +159,7 @@ __global__ __launch_bounds__(NTHREADS) void gemm_tn_kernel(const GemmGroup g) {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int wm = wave >> 1, wn = wave & 1;
     int local;
-    const GemmProblem& P = find_problem(g, xcd_remap(blockIdx.x, g.total_tiles), local);
+    const GemmProblem& P = find_problem(g, xcd_remap256(blockIdx.x, g.total_tiles), local);
     const int m0 = (local / P.tiles_n) * BM, n0 = (local % P.tiles_n) * BN;
     const int K = P.K, nkt = (K + BK - 1) / BK;
 
@@ -293,10 +287,6 @@ static int check_group(const GemmGroup& g, bool tn) {
 }
 
 int g_rgqa_force_gemm128 = 0;
-bool gemm_nt256_eligible(const GemmGroup& g, int out_f32);
-int launch_gemm_nt256_bf16(GemmGroup& g, hipStream_t s);
-int launch_gemm_nt256_f32out(GemmGroup& g, hipStream_t s);
-int launch_gemm_nt256_any(GemmGroup& g, int out_f32, hipStream_t s);
 
 int launch_gemm_nt_bf16(GemmGroup& g, int out_f32, hipStream_t s) {
     int r = check_group(g, false);
@@ -321,9 +311,6 @@ int launch_gemm_nt_bf16(GemmGroup& g, int out_f32, hipStream_t s) {
     RGQA_LAUNCH_CHECK("gemm_nt_kernel");
     return RGQA_OK;
 }
-
-bool gemm_tn_dma_eligible(const GemmGroup& g);
-int launch_gemm_tn_dma_bf16(GemmGroup& g, hipStream_t s);
 
 int launch_gemm_tn_bf16(GemmGroup& g, int out_f32, hipStream_t s) {
     int r = check_group(g, true);

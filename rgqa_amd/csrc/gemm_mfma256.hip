@@ -24,8 +24,7 @@ bool gemm_nt256_eligible(const GemmGroup& g, int out_f32) {
         }
         return true;
     }
-    if (!(epi == EPI_BIAS || epi == EPI_GELU || epi == EPI_RESID_DROP || epi == EPI_DGELU || epi == EPI_ADD || epi == EPI_TANH || epi == EPI_DTANH ||
-          epi == EPI_RELU || epi == EPI_RELU_DROP || epi == EPI_DRELU_DROP)) return false;
+    if (!epi_in(NtEpis{}, epi)) return false;
     for (int i = 0; i < g.count; ++i) {
         const GemmProblem& p = g.p[i];
         if (p.epi != epi || p.K % TK != 0 || p.K < TK || (p.ldc % 8) != 0 || (p.N % 8) != 0) return false;
@@ -80,112 +79,39 @@ int launch_gemm_nt256_probe(GemmGroup& g, int mt, hipStream_t s) {
 
 int launch_gemm_nt256_f32out(GemmGroup& g, hipStream_t s) { return g.b_kn ? launch256<float, EPI_BIAS, 2, false, true>(g, s) : launch256<float, EPI_BIAS, 2, false>(g, s); }
 
+// every caller has passed gemm_nt256_eligible (launch_gemm_nt_bf16 -> launch_gemm_nt256_any): the epilogue is one of NtEpis
 int launch_gemm_nt256_bf16(GemmGroup& g, hipStream_t s) {
     long tiles = 0;
     int mt = pick_mt(g, tiles);
     if (g_rgqa_force_mt) mt = g_rgqa_force_mt;
-    if (g.b_kn) {       // B operands stored [K, N] (dgrad on the weight as it lies): the epilogues a dgrad uses
-        switch (g.p[0].epi) {
-            case EPI_BIAS: return launch256_mt<bf16_t, EPI_BIAS, false, true>(g, mt, s);
-            case EPI_DGELU: return launch256_mt<bf16_t, EPI_DGELU, false, true>(g, mt, s);
-            case EPI_ADD: return launch256_mt<bf16_t, EPI_ADD, false, true>(g, mt, s);
-            case EPI_DTANH: return launch256_mt<bf16_t, EPI_DTANH, false, true>(g, mt, s);
-            default: rgqa_set_error("gemm: no [K, N]-operand kernel for epilogue %d", g.p[0].epi); return RGQA_ERR_ARG;
-        }
+    if (g.b_kn) return launch256_epi<bf16_t, false, true>(NtKnEpis{}, "gemm: no [K, N]-operand kernel", g, mt, s);
+    const bool lnf = g.p[0].epi == EPI_RESID_DROP && g.p[0].ln_tk != nullptr;       // the LayerNorm behind the dense layer rides in the launch: every problem or none
+    if (g.p[0].epi == EPI_RESID_DROP)
+        for (int i = 1; i < g.count; ++i) RGQA_REQUIRE((g.p[i].ln_tk != nullptr) == lnf, "gemm: the fused LayerNorm must be set on every problem of a group or on none");
+    if (lnf) {
+        for (int i = 0; i < g.count; ++i)
+            RGQA_REQUIRE(g.p[i].N == 768 && g.p[i].ln_g && g.p[i].ln_b && g.p[i].ln_y && g.p[i].ln_mean && g.p[i].ln_rstd, "gemm: the fused LayerNorm needs N == 768 and all of its operands");
+        return launch256_mt<bf16_t, EPI_RESID_DROP, false, false, true>(g, mt, s);
     }
-    switch (g.p[0].epi) {
-        case EPI_BIAS: return launch256_mt<bf16_t, EPI_BIAS, false>(g, mt, s);
-        case EPI_GELU: return launch256_mt<bf16_t, EPI_GELU, false>(g, mt, s);
-        case EPI_RESID_DROP: {
-            bool lnf = g.p[0].ln_tk != nullptr;            // the LayerNorm behind the dense layer rides in the launch: every problem or none
-            for (int i = 1; i < g.count; ++i) RGQA_REQUIRE((g.p[i].ln_tk != nullptr) == lnf, "gemm: the fused LayerNorm must be set on every problem of a group or on none");
-            if (lnf) {
-                for (int i = 0; i < g.count; ++i)
-                    RGQA_REQUIRE(g.p[i].N == 768 && g.p[i].ln_g && g.p[i].ln_b && g.p[i].ln_y && g.p[i].ln_mean && g.p[i].ln_rstd, "gemm: the fused LayerNorm needs N == 768 and all of its operands");
-                return launch256_mt<bf16_t, EPI_RESID_DROP, false, false, true>(g, mt, s);
-            }
-            return launch256_mt<bf16_t, EPI_RESID_DROP, false>(g, mt, s);
-        }
-        case EPI_DGELU: return launch256_mt<bf16_t, EPI_DGELU, false>(g, mt, s);
-        case EPI_TANH: return launch256_mt<bf16_t, EPI_TANH, false>(g, mt, s);
-        case EPI_DTANH: return launch256_mt<bf16_t, EPI_DTANH, false>(g, mt, s);
-        case EPI_RELU: return launch256_mt<bf16_t, EPI_RELU, false>(g, mt, s);
-        case EPI_RELU_DROP: return launch256_mt<bf16_t, EPI_RELU_DROP, false>(g, mt, s);
-        case EPI_DRELU_DROP: return launch256_mt<bf16_t, EPI_DRELU_DROP, false>(g, mt, s);
-        default: return launch256_mt<bf16_t, EPI_ADD, false>(g, mt, s);
-    }
+    return launch256_epi<bf16_t, false, false>(NtEpis{}, "gemm: no LDS-DMA kernel", g, mt, s);
 }
 
-// ============================================================================ split-K for skinny NT problems
-// The [CLS]-row tail of the last layer, the pooler and the answer head are GEMMs of M = B rows (256 in training): 3-12 tiles on a 256-CU chip,
-// each walking a contraction of 1,536-3,072 alone (42 us for 1.2 GFLOP).  Their contraction is cut into S <= 12 slices that run as the S problems
-// of ONE grouped launch of the f32-result kernel (64-row tiles: 4 x N/256 x S blocks, 4-5 K-steps each) into f32 partial tiles, and one pass
-// sums the slices in slice order - a fixed order: bit-reproducible - and applies the epilogue (bias, activation, dropout, residual, second
-// output) with the shared element-wise epilogue of gemm.h.  Two launches of ~6 us for one of 25-42.
-// S depends on K alone and the path is chosen by CALL SITE (the caller hands scratch over), never by M: a batch of more than 256 rows runs as
-// row groups of <= 256 rows, each with the same S, so a sample's arithmetic does not depend on the batch it is in (eval at B = 1024 and
-// training at B = 256 fold the same slices in the same order; tests/test_gpu_engine.py::test_full_size_batch_independence...).
-#define SPLITK_ROWS 256
+// ============================================================================ split-K for skinny NT problems (gemm_nt256.h), bf16 operands
 int g_rgqa_nt_splitk = 1;     // rgqa_debug_set key 7: 0 = skinny problems stay whole
-template <typename OutT>
-__global__ __launch_bounds__(256) void splitk_finish_kernel(const GemmProblem P, const DropCfg drop, const float* __restrict__ part, int S, int ldp, size_t slice_stride,
-                                                            int m_base, int rows) {
-    const int nq = P.N >> 2;
-    const long i = (long)blockIdx.x * 256 + threadIdx.x;
-    if (i >= (long)rows * nq) return;
-    const int ml = (int)(i / nq), n0 = (int)(i % nq) << 2;
-    const float* src = part + (size_t)ml * ldp + n0;
-    float v[4] = {0.f, 0.f, 0.f, 0.f};
-    for (int s = 0; s < S; ++s) {
-        float t[4]; load4(src + (size_t)s * slice_stride, t);
-        v[0] += t[0]; v[1] += t[1]; v[2] += t[2]; v[3] += t[3];
-    }
-    gemm_epilogue4_e<OutT, bf16_t>(P, P.epi, drop, m_base + ml, n0, v);     // global row: addresses and the dropout stream are those of the whole problem
-}
-static int splitk_slices(const GemmGroup& g, int out_f32) {
-    if (!g_rgqa_nt_splitk || g.count != 1 || g.a_f32 || g.splitk_ws == nullptr || g.stamps != nullptr) return 0;
-    const GemmProblem& p = g.p[0];
-    if (p.K < 1536 || (p.K % TK) != 0 || (p.N % 8) != 0 || (p.ldc % 4) != 0 || p.Cb != nullptr) return 0;
-    if (out_f32 && p.epi != EPI_BIAS) return 0;
-    if (p.epi == EPI_ACCUM || (epi_needs_aux(p.epi) && (p.aux == nullptr || (p.ldaux % 4) != 0))) return 0;
-    int S = (p.K / TK) / 4;
-    if (S > GEMM_NT_MAX_PROBLEMS) S = GEMM_NT_MAX_PROBLEMS;
-    const int rows = p.M < SPLITK_ROWS ? p.M : SPLITK_ROWS;
-    if (S < 2 || (size_t)S * rows * p.N > g.splitk_floats) return 0;
-    return S;
-}
-static int launch_gemm_nt_splitk(GemmGroup& g, int S, int out_f32, hipStream_t s) {
-    const GemmProblem P = g.p[0];
-    const int steps = P.K / TK, ldp = P.N;
-    for (int m0 = 0; m0 < P.M; m0 += SPLITK_ROWS) {         // row groups: the scratch is reused, the launches are ordered by the stream
-        const int rows = P.M - m0 < SPLITK_ROWS ? P.M - m0 : SPLITK_ROWS;
-        const size_t stride = (size_t)rows * ldp;
-        GemmGroup g2; memset(&g2, 0, sizeof g2);
-        g2.count = S; g2.drop = g.drop; g2.b_kn = g.b_kn;
-        for (int i = 0, k0 = 0; i < S; ++i) {
-            const int ks = (steps / S + (i < steps % S ? 1 : 0)) * TK;
-            GemmProblem& q = g2.p[i];
-            q.A = reinterpret_cast<const bf16_t*>(P.A) + (size_t)m0 * P.lda + k0; q.lda = P.lda;
-            q.B = reinterpret_cast<const bf16_t*>(P.B) + (g.b_kn ? (size_t)k0 * P.ldb : (size_t)k0); q.ldb = P.ldb;
-            q.C = g.splitk_ws + (size_t)i * stride; q.ldc = ldp;
-            q.M = rows; q.N = P.N; q.K = ks; q.epi = EPI_BIAS;
-            k0 += ks;
-        }
+struct SplitKBf16 {
+    using T = bf16_t;
+    static constexpr int KSTEP = TK, MIN_K = 1536;
+    static constexpr bool CHECKED = true;
+    static int slices(GemmGroup& g2, hipStream_t s) {
         RGQA_REQUIRE(gemm_nt256_eligible(g2, 1), "gemm split-K: internal eligibility mismatch");
-        if (int r = launch_gemm_nt256_f32out(g2, s)) return r;
-        const long n4 = (long)rows * (P.N >> 2);
-        const int blocks = (int)((n4 + 255) / 256);
-        if (out_f32) hipLaunchKernelGGL((splitk_finish_kernel<float>), dim3(blocks), dim3(256), 0, s, P, g.drop, g.splitk_ws, S, ldp, stride, m0, rows);
-        else hipLaunchKernelGGL((splitk_finish_kernel<bf16_t>), dim3(blocks), dim3(256), 0, s, P, g.drop, g.splitk_ws, S, ldp, stride, m0, rows);
-        RGQA_LAUNCH_CHECK("splitk_finish_kernel");
+        return launch_gemm_nt256_f32out(g2, s);
     }
-    return RGQA_OK;
-}
+};
 // the bf16 NT entry of the LDS-DMA kernels: skinny single problems take the split-K path when the caller provides scratch
 int launch_gemm_nt256_any(GemmGroup& g, int out_f32, hipStream_t s) {
-    if (const int S = splitk_slices(g, out_f32)) {
+    if (const int S = splitk_slices<SplitKBf16>(g, out_f32)) {
         RGQA_REQUIRE(g.p[0].ln_tk == nullptr, "gemm: the split-K path has no fused LayerNorm");
-        return launch_gemm_nt_splitk(g, S, out_f32, s);
+        return launch_gemm_nt_splitk<SplitKBf16>(g, S, out_f32, s);
     }
     return out_f32 ? launch_gemm_nt256_f32out(g, s) : launch_gemm_nt256_bf16(g, s);
 }
@@ -200,7 +126,6 @@ int launch_gemm_nt256_any(GemmGroup& g, int out_f32, hipStream_t s) {
 // dispatcher balances the unequal (lang / visn / shared) problems of one launch over the 256 CUs.
 #define RGQA_TN_PIPE 3     // A fragments through a register ring 3 deep (in situ -0.26 ms per step against the plain loop; depth 4 spills)
 #define WM 128
-#define WN 256
 // MTW = 16-row m-tiles per wave (2 waves along M): output tile WMV = 32*MTW rows x 256 columns.
 //   MTW = 4: 128 x 256, 3-slot ring (48 KiB per K-step per CU);  MTW = 8: 256 x 256, 2 slots of 64 KiB: twice the MFMAs per
 //   DMA byte.  The loop is bound by what the LDS-DMA path delivers per CU (~50 GB/s), not by the MFMAs, so the taller tile
@@ -219,34 +144,7 @@ __global__ __launch_bounds__(T256_THREADS) void gemm_tn_dma_kernel(const GemmGro
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wm = wave >> 2, wn = wave & 3;
-    // Block id -> tile.  The launcher sorts the problems by contraction length; problems of equal length form a class, and the ids of a class
-    // are re-dealt so that the blocks of one XCD (equal id mod 8, dispatched in id order) walk ONE contiguous run of the class's tile list:
-    // a run is a compact piece of one weight matrix - M-tiles of one N-tile first - whose tiles stream the same operand rows at the same time
-    // through that XCD's L2.  (Per problem instead of per class, the runs were 3-5 tiles: L2 hit rate 0.39.)  Every XCD gets an eighth of
-    // every class, so the XCDs stay balanced whatever the mix of lengths.
-    const int tile0 = blockIdx.x;
-    int p0 = 0;
-#pragma unroll
-    for (int i = 1; i < GEMM_MAX_PROBLEMS; ++i)
-        if (i < g.count && tile0 >= g.p[i].tile_start) p0 = i;
-    const int K0 = g.p[p0].K;
-    int c_lo = g.p[p0].tile_start, c_hi = g.total_tiles;
-#pragma unroll
-    for (int i = 0; i < GEMM_MAX_PROBLEMS; ++i)
-        if (i < g.count) {
-            if (g.p[i].K == K0) c_lo = min(c_lo, g.p[i].tile_start);
-            else if (g.p[i].K < K0) c_hi = min(c_hi, g.p[i].tile_start);
-        }
-    const int tile = c_lo + xcd_remap256(tile0 - c_lo, c_hi - c_lo);
-    int pi = 0;
-#pragma unroll
-    for (int i = 1; i < GEMM_MAX_PROBLEMS; ++i)
-        if (i < g.count && tile >= g.p[i].tile_start) pi = i;
-    const GemmProblem& P = g.p[pi];
-    const int tiles_m = cdiv(P.M, WMV);
-    const int tix = tile - P.tile_start;
-    const int local = (tix % tiles_m) * P.tiles_n + (tix / tiles_m);     // back to the m-major id used below
-    const int m0 = (local / P.tiles_n) * WMV, n0 = (local % P.tiles_n) * WN;
+    TN_TILE_MAP(g, WMV, P, local, m0, n0)
     // contraction length need not be a multiple of the K-step (packed language rows): in the last, partial step the A rows
     // past K come from a zero line (they also feed the bias column sums) and the B rows past K re-read row K-1 (finite data
     // times zero), so no lane predicates its DMA.
@@ -354,36 +252,7 @@ __global__ __launch_bounds__(T256_THREADS) void gemm_tn_dma_kernel(const GemmGro
     }
     };
     if (do_cs) kloop(std::true_type{}); else kloop(std::false_type{});
-    float* Cc = reinterpret_cast<float*>(P.C);
-    float* cs_out = P.colsum_out;
-    const int ldc = P.ldc;
-    constexpr bool accum = ACCUM != 0;
-    if (do_cs && (lane >> 4) == 0) {
-#pragma unroll
-        for (int tm = 0; tm < MTW; ++tm) {
-            const int m = m0 + wm * (16 * MTW) + tm * 16 + (lane & 15);
-            if (m < P.M) cs_out[m] = accum ? cs_out[m] + cs[tm][0] : cs[tm][0];
-        }
-    }
-    const int fr = lane & 15, fq = lane >> 4;
-#pragma unroll
-    for (int tm = 0; tm < MTW; ++tm) {
-        const int m = m0 + wm * (16 * MTW) + tm * 16 + fr;
-#pragma unroll
-        for (int tn = 0; tn < 4; ++tn) {
-            const int n = n0 + wn * 64 + tn * 16 + 4 * fq;
-            if (m < P.M && n < P.N) {
-                float* c = Cc + (size_t)m * ldc + n;
-                float v[4] = {acc[tm][tn][0], acc[tm][tn][1], acc[tm][tn][2], acc[tm][tn][3]};
-                if (n + 3 < P.N) {
-                    if (accum) { float o[4]; load4(c, o); v[0] += o[0]; v[1] += o[1]; v[2] += o[2]; v[3] += o[3]; }
-                    store4(c, v);
-                } else {
-                    for (int i = 0; i < P.N - n; ++i) c[i] = accum ? c[i] + v[i] : v[i];
-                }
-            }
-        }
-    }
+    TN_STORE_TILE(ACCUM, MTW, P, do_cs, lane, wm, wn, m0, n0, acc, cs)
 }
 
 bool gemm_tn_dma_eligible(const GemmGroup& g) {
@@ -399,22 +268,8 @@ bool gemm_tn_dma_eligible(const GemmGroup& g) {
     return tiles >= 1;
 }
 
-int g_rgqa_tn_mtw = 0;     // rgqa_debug_set key 4: force the wgrad tile height (4 = 128 rows, 8 = 256 rows); 0 = default
-template <int ACCUM, int MTW>
-static int launch_tn(GemmGroup& g, hipStream_t s) {
-    constexpr int WMV = 32 * MTW, LDS_BYTES = (MTW == 4 ? 3 : 2) * (TK * WMV * 2 + TK * WN * 2);
-    static bool attr_set = false;
-    if (!attr_set) {
-        RGQA_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_tn_dma_kernel<ACCUM, MTW>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES));
-        attr_set = true;
-    }
-    gemm_group_finalize(g, WMV, WN);
-    hipLaunchKernelGGL((gemm_tn_dma_kernel<ACCUM, MTW>), dim3(g.total_tiles), dim3(T256_THREADS), LDS_BYTES, s, g);
-    RGQA_LAUNCH_CHECK("gemm_tn_dma_kernel");
-    return RGQA_OK;
-}
-
-int launch_gemm_tn_dma_bf16(GemmGroup& g, hipStream_t s) {
+// host prologue of both LDS-DMA wgrad launchers (this one and gemm_x3.hip's)
+int gemm_tn_prepare(GemmGroup& g, int bm, int bn) {
     // longest contraction first: block ids are dispatched in order, so the dispatcher does LPT balancing
     for (int i = 1; i < g.count; ++i)
         for (int j = i; j > 0 && g.p[j].K > g.p[j - 1].K; --j) { GemmProblem t = g.p[j]; g.p[j] = g.p[j - 1]; g.p[j - 1] = t; }
@@ -424,6 +279,26 @@ int launch_gemm_tn_dma_bf16(GemmGroup& g, hipStream_t s) {
         RGQA_HIP(hipMemset(zero_line, 0, 256));
     }
     g.zeros = zero_line;
+    gemm_group_finalize(g, bm, bn);
+    return RGQA_OK;
+}
+
+int g_rgqa_tn_mtw = 0;     // rgqa_debug_set key 4: force the wgrad tile height (4 = 128 rows, 8 = 256 rows); 0 = default
+template <int ACCUM, int MTW>
+static int launch_tn(GemmGroup& g, hipStream_t s) {
+    constexpr int WMV = 32 * MTW, LDS_BYTES = (MTW == 4 ? 3 : 2) * (TK * WMV * 2 + TK * WN * 2);
+    static bool attr_set = false;
+    if (!attr_set) {
+        RGQA_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_tn_dma_kernel<ACCUM, MTW>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES));
+        attr_set = true;
+    }
+    if (int r = gemm_tn_prepare(g, WMV, WN)) return r;
+    hipLaunchKernelGGL((gemm_tn_dma_kernel<ACCUM, MTW>), dim3(g.total_tiles), dim3(T256_THREADS), LDS_BYTES, s, g);
+    RGQA_LAUNCH_CHECK("gemm_tn_dma_kernel");
+    return RGQA_OK;
+}
+
+int launch_gemm_tn_dma_bf16(GemmGroup& g, hipStream_t s) {
     // 256-row tiles when every problem has at least 256 output rows and the launch still spreads over >= half the CUs
     int mtw = g_rgqa_tn_mtw;
     if (mtw != 4 && mtw != 8) {

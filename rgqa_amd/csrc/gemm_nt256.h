@@ -14,6 +14,7 @@
 // the per-lane SOURCE address (the LDS destination of an LDS-DMA is lane-linear).  The next K-step's 64 KiB are in flight while
 // the current one is consumed.
 #pragma once
+#include <string.h>
 #include "gemm256_dev.h"
 
 // One K-step of MFMAs for a wave's (16*MT) x 64 slice.  The A fragments come through a register ring PD deep - the LDS read for
@@ -446,4 +447,94 @@ static int launch256_mt(GemmGroup& g, int mt, hipStream_t s) {
         case 4: return launch256<OutT, EPI, 4, X3, NN, LNF>(g, s);
         default: return launch256<OutT, EPI, 2, X3, NN, LNF>(g, s);
     }
+}
+
+// ---- runtime epilogue -> instantiation, for a compile-time list of the epilogues a launcher may run.  The lists are also what eligibility asks.
+template <int... E> struct EpiList {};
+using NtEpis = EpiList<EPI_BIAS, EPI_GELU, EPI_TANH, EPI_RESID_DROP, EPI_DGELU, EPI_ADD, EPI_DTANH, EPI_RELU, EPI_RELU_DROP, EPI_DRELU_DROP>;   // bf16_t / sf32 results
+using NtKnEpis = EpiList<EPI_BIAS, EPI_DGELU, EPI_ADD, EPI_DTANH>;     // B operands stored [K, N] (dgrad on the weight as it lies): the epilogues a dgrad uses
+template <int... E> static inline bool epi_in(EpiList<E...>, int epi) { return ((epi == E) || ...); }
+template <typename OutT, bool X3, bool NN, int... E>
+static int launch256_epi(EpiList<E...>, const char* what, GemmGroup& g, int mt, hipStream_t s) {
+    const int epi = g.p[0].epi;
+    int r = RGQA_ERR_ARG;
+    if (!((epi == E && ((r = launch256_mt<OutT, E, X3, NN>(g, mt, s)), true)) || ...)) rgqa_set_error("%s for epilogue %d", what, epi);
+    return r;
+}
+
+// ============================================================================ split-K for skinny NT problems, either operand precision
+// The [CLS]-row tail of the last layer, the pooler and the answer head are GEMMs of M = B rows (256 in training), the BUTD engine's per-sample GEMMs too -
+// above all the GRU's per-token h W_hh^T (K = 1024) and its dgrad (K = 3072): 3-12 tiles on a 256-CU chip, each walking a contraction of 768-3,072 alone
+// (bf16: 42 us for 1.2 GFLOP; split f32, at twice the K-steps: 46 us for the GRU's forward product, 78 us for the tail FFN2).  Their contraction is cut into
+// S = K / 256 <= 12 slices that run as the S problems of ONE grouped launch of the f32-result kernel (64-row tiles: 4 x N/256 x S blocks) into f32 partial
+// tiles, and one pass sums the slices in slice order - a fixed order: bit-reproducible - and applies the epilogue (bias, activation, dropout, residual, second
+// output, bf16 images) with the shared element-wise epilogue of gemm.h.  Two launches of ~6 us for one of 25-78.
+// S depends on K alone and the path is chosen by CALL SITE (the caller hands scratch over), never by M: a batch of more than 256 rows runs as
+// row groups of <= 256 rows, each with the same S, so a sample's arithmetic does not depend on the batch it is in (eval at B = 1024 and
+// training at B = 256 fold the same slices in the same order; tests/test_gpu_engine.py::test_full_size_batch_independence...).
+//
+// Op, the operand policy (SplitKBf16 in gemm_mfma256.hip, SplitKX3 in gemm_x3.hip):
+//   T        element type of A / B, and of C / aux unless the result is f32
+//   KSTEP    contraction elements per K-step of the slice kernel (slices are whole K-steps); MIN_K: shorter contractions stay whole
+//   CHECKED  the launcher has NOT validated layouts: a_f32, a bf16 image (Cb), ldc % 4 and ldaux % 4 are looked at here, and b_kn is passed on
+//   slices(g2, s)   runs the S slice problems: launch256<float, EPI_BIAS, 2, X3, NN>
+#define SPLITK_ROWS 256
+template <typename OutT, typename AuxT>
+__global__ __launch_bounds__(256) void splitk_finish_kernel(const GemmProblem P, const DropCfg drop, const float* __restrict__ part, int S, int ldp, size_t slice_stride,
+                                                            int m_base, int rows) {
+    const int nq = P.N >> 2;
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= (long)rows * nq) return;
+    const int ml = (int)(i / nq), n0 = (int)(i % nq) << 2;
+    const float* src = part + (size_t)ml * ldp + n0;
+    float v[4] = {0.f, 0.f, 0.f, 0.f};
+    for (int s = 0; s < S; ++s) {
+        float t[4]; load4(src + (size_t)s * slice_stride, t);
+        v[0] += t[0]; v[1] += t[1]; v[2] += t[2]; v[3] += t[3];
+    }
+    gemm_epilogue4_e<OutT, AuxT>(P, P.epi, drop, m_base + ml, n0, v);     // global row: addresses and the dropout stream are those of the whole problem
+}
+// number of slices, 0 = the problem stays whole
+template <typename Op>
+static int splitk_slices(const GemmGroup& g, int out_f32) {
+    if (!g_rgqa_nt_splitk || g.count != 1 || g.splitk_ws == nullptr || g.stamps != nullptr) return 0;
+    const GemmProblem& p = g.p[0];
+    if (p.K < Op::MIN_K || (p.K % Op::KSTEP) != 0 || (p.N % 8) != 0) return 0;
+    if (Op::CHECKED && (g.a_f32 || (p.ldc % 4) != 0 || p.Cb != nullptr || (epi_needs_aux(p.epi) && (p.ldaux % 4) != 0))) return 0;
+    if (out_f32 && p.epi != EPI_BIAS) return 0;
+    if (p.epi == EPI_ACCUM || (epi_needs_aux(p.epi) && p.aux == nullptr)) return 0;
+    int S = p.K / 256;
+    if (S > GEMM_NT_MAX_PROBLEMS) S = GEMM_NT_MAX_PROBLEMS;
+    const int rows = p.M < SPLITK_ROWS ? p.M : SPLITK_ROWS;
+    if (S < 2 || (size_t)S * rows * p.N > g.splitk_floats) return 0;
+    return S;
+}
+template <typename Op>
+static int launch_gemm_nt_splitk(GemmGroup& g, int S, int out_f32, hipStream_t s) {
+    using T = typename Op::T;
+    const GemmProblem P = g.p[0];
+    const int steps = P.K / Op::KSTEP, ldp = P.N;
+    const int b_kn = Op::CHECKED ? g.b_kn : 0;
+    for (int m0 = 0; m0 < P.M; m0 += SPLITK_ROWS) {         // row groups: the scratch is reused, the launches are ordered by the stream
+        const int rows = P.M - m0 < SPLITK_ROWS ? P.M - m0 : SPLITK_ROWS;
+        const size_t stride = (size_t)rows * ldp;
+        GemmGroup g2; memset(&g2, 0, sizeof g2);
+        g2.count = S; g2.drop = g.drop; g2.b_kn = b_kn;
+        for (int i = 0, k0 = 0; i < S; ++i) {
+            const int ks = (steps / S + (i < steps % S ? 1 : 0)) * Op::KSTEP;
+            GemmProblem& q = g2.p[i];
+            q.A = reinterpret_cast<const T*>(P.A) + (size_t)m0 * P.lda + k0; q.lda = P.lda;       // split f32: KSTEP-aligned columns are whole 128-byte lines
+            q.B = reinterpret_cast<const T*>(P.B) + (b_kn ? (size_t)k0 * P.ldb : (size_t)k0); q.ldb = P.ldb;
+            q.C = g.splitk_ws + (size_t)i * stride; q.ldc = ldp;
+            q.M = rows; q.N = P.N; q.K = ks; q.epi = EPI_BIAS;
+            k0 += ks;
+        }
+        if (int r = Op::slices(g2, s)) return r;
+        const long n4 = (long)rows * (P.N >> 2);
+        const int blocks = (int)((n4 + 255) / 256);
+        if (out_f32) hipLaunchKernelGGL((splitk_finish_kernel<float, T>), dim3(blocks), dim3(256), 0, s, P, g.drop, g.splitk_ws, S, ldp, stride, m0, rows);
+        else hipLaunchKernelGGL((splitk_finish_kernel<T, T>), dim3(blocks), dim3(256), 0, s, P, g.drop, g.splitk_ws, S, ldp, stride, m0, rows);
+        RGQA_LAUNCH_CHECK("splitk_finish_kernel");
+    }
+    return RGQA_OK;
 }

@@ -13,68 +13,14 @@
 // every problem: K % 32 == 0, rows of A / W / C / aux whole 128-byte lines (ld % 32 == 0, bases 128-byte aligned), N % 8 == 0
 static bool x3_aligned(const void* p, int ld) { return p == nullptr || ((((uintptr_t)p) & 127) == 0 && (ld % 32) == 0); }
 
-// ---------------------------------------------------------------------------------------------------------------- split-K for skinny problems (round 6)
-// The [CLS]-row GEMMs of the LXMERT engines (tail FFN, pooler, answer head: M = B rows) and the BUTD engine's per-sample GEMMs - above all the GRU's
-// per-token h W_hh^T (M = B, K = 1024) and its dgrad (K = 3072) - are 3-12 tiles on a 256-CU chip, each walking a long contraction alone: 46 us for the
-// GRU's forward product, 78 us for the tail FFN2, in split f32 twice the K-steps of the bf16 kernels.  As the bf16 launcher does since round 4
-// (gemm_mfma256.hip): the contraction is cut into S = K / 256 <= 12 slices that run as the S problems of ONE grouped launch of the f32-result kernel,
-// and one pass folds the slices in slice order (bit-reproducible) and applies the epilogue - bias, activation, dropout, residual, the second output and the
-// bf16 images.  Chosen by call site (the caller hands scratch over), never by M; more than 256 rows run as row groups of 256.
-#define X3_SPLITK_ROWS 256
-extern int g_rgqa_nt_splitk;     // rgqa_debug_set key 7
-template <typename OutT>
-__global__ __launch_bounds__(256) void splitk_finish_x3_kernel(const GemmProblem P, const DropCfg drop, const float* __restrict__ part, int S, int ldp, size_t slice_stride,
-                                                               int m_base, int rows) {
-    const int nq = P.N >> 2;
-    const long i = (long)blockIdx.x * 256 + threadIdx.x;
-    if (i >= (long)rows * nq) return;
-    const int ml = (int)(i / nq), n0 = (int)(i % nq) << 2;
-    const float* src = part + (size_t)ml * ldp + n0;
-    float v[4] = {0.f, 0.f, 0.f, 0.f};
-    for (int s = 0; s < S; ++s) {
-        float t[4]; load4(src + (size_t)s * slice_stride, t);
-        v[0] += t[0]; v[1] += t[1]; v[2] += t[2]; v[3] += t[3];
-    }
-    gemm_epilogue4_e<OutT, sf32>(P, P.epi, drop, m_base + ml, n0, v);
-}
-static int x3_splitk_slices(const GemmGroup& g, int out_f32) {
-    if (!g_rgqa_nt_splitk || g.count != 1 || g.splitk_ws == nullptr || g.stamps != nullptr) return 0;
-    const GemmProblem& p = g.p[0];
-    if (p.K < 768 || (p.K % 32) != 0 || (p.N % 8) != 0) return 0;
-    if (out_f32 && p.epi != EPI_BIAS) return 0;
-    if (p.epi == EPI_ACCUM || (epi_needs_aux(p.epi) && p.aux == nullptr)) return 0;
-    int S = p.K / 256;
-    if (S > GEMM_NT_MAX_PROBLEMS) S = GEMM_NT_MAX_PROBLEMS;
-    const int rows = p.M < X3_SPLITK_ROWS ? p.M : X3_SPLITK_ROWS;
-    if (S < 2 || (size_t)S * rows * p.N > g.splitk_floats) return 0;
-    return S;
-}
-static int launch_gemm_nt_x3_splitk(GemmGroup& g, int S, int out_f32, hipStream_t s) {
-    const GemmProblem P = g.p[0];
-    const int steps = P.K / 32, ldp = P.N;              // K-steps of 32 contraction elements (64 staged bf16 columns)
-    for (int m0 = 0; m0 < P.M; m0 += X3_SPLITK_ROWS) {
-        const int rows = P.M - m0 < X3_SPLITK_ROWS ? P.M - m0 : X3_SPLITK_ROWS;
-        const size_t stride = (size_t)rows * ldp;
-        GemmGroup g2; memset(&g2, 0, sizeof g2);
-        g2.count = S; g2.drop = g.drop;
-        for (int i = 0, k0 = 0; i < S; ++i) {
-            const int ks = (steps / S + (i < steps % S ? 1 : 0)) * 32;
-            GemmProblem& q = g2.p[i];
-            q.A = reinterpret_cast<const sf32*>(P.A) + (size_t)m0 * P.lda + k0; q.lda = P.lda;      // 32-aligned columns: whole 128-byte lines
-            q.B = reinterpret_cast<const sf32*>(P.B) + k0; q.ldb = P.ldb;
-            q.C = g.splitk_ws + (size_t)i * stride; q.ldc = ldp;
-            q.M = rows; q.N = P.N; q.K = ks; q.epi = EPI_BIAS;
-            k0 += ks;
-        }
-        if (int r = launch256<float, EPI_BIAS, 2, true>(g2, s)) return r;
-        const long n4 = (long)rows * (P.N >> 2);
-        const int blocks = (int)((n4 + 255) / 256);
-        if (out_f32) hipLaunchKernelGGL((splitk_finish_x3_kernel<float>), dim3(blocks), dim3(256), 0, s, P, g.drop, g.splitk_ws, S, ldp, stride, m0, rows);
-        else hipLaunchKernelGGL((splitk_finish_x3_kernel<sf32>), dim3(blocks), dim3(256), 0, s, P, g.drop, g.splitk_ws, S, ldp, stride, m0, rows);
-        RGQA_LAUNCH_CHECK("splitk_finish_x3_kernel");
-    }
-    return RGQA_OK;
-}
+// split-K for skinny problems (gemm_nt256.h), split-f32 operands: K-steps of 32 contraction elements (64 staged bf16 columns); the checks of launch_gemm_nt_x3
+// have validated every layout before the planner runs
+struct SplitKX3 {
+    using T = sf32;
+    static constexpr int KSTEP = 32, MIN_K = 768;
+    static constexpr bool CHECKED = false;
+    static int slices(GemmGroup& g2, hipStream_t s) { return launch256<float, EPI_BIAS, 2, true>(g2, s); }
+};
 
 int launch_gemm_nt_x3(GemmGroup& g, int out_f32, hipStream_t s) {
     RGQA_REQUIRE(g.count >= 1 && g.count <= GEMM_NT_MAX_PROBLEMS, "gemm_x3: bad problem count %d", g.count);
@@ -93,7 +39,7 @@ int launch_gemm_nt_x3(GemmGroup& g, int out_f32, hipStream_t s) {
         }
         if (epi_needs_aux(epi)) RGQA_REQUIRE(p.aux != nullptr && x3_aligned(p.aux, p.ldaux), "gemm_x3[%d]: epilogue %d needs a split-f32 aux operand (ldaux=%d)", i, epi, p.ldaux);
     }
-    if (const int S = x3_splitk_slices(g, out_f32)) return launch_gemm_nt_x3_splitk(g, S, out_f32, s);
+    if (const int S = splitk_slices<SplitKX3>(g, out_f32)) return launch_gemm_nt_splitk<SplitKX3>(g, S, out_f32, s);
     long tiles = 0;
     int mt = pick_mt(g, tiles);
     if (g_rgqa_force_mt) mt = g_rgqa_force_mt;
@@ -101,19 +47,7 @@ int launch_gemm_nt_x3(GemmGroup& g, int out_f32, hipStream_t s) {
         RGQA_REQUIRE(epi == EPI_BIAS, "gemm_x3: f32 results take the plain bias epilogue only");
         return launch256_mt<float, EPI_BIAS, true>(g, mt, s);
     }
-    switch (epi) {
-        case EPI_BIAS: return launch256_mt<sf32, EPI_BIAS, true>(g, mt, s);
-        case EPI_GELU: return launch256_mt<sf32, EPI_GELU, true>(g, mt, s);
-        case EPI_TANH: return launch256_mt<sf32, EPI_TANH, true>(g, mt, s);
-        case EPI_RESID_DROP: return launch256_mt<sf32, EPI_RESID_DROP, true>(g, mt, s);
-        case EPI_DGELU: return launch256_mt<sf32, EPI_DGELU, true>(g, mt, s);
-        case EPI_ADD: return launch256_mt<sf32, EPI_ADD, true>(g, mt, s);
-        case EPI_DTANH: return launch256_mt<sf32, EPI_DTANH, true>(g, mt, s);
-        case EPI_RELU: return launch256_mt<sf32, EPI_RELU, true>(g, mt, s);                     // BUTD (butd.py:8-26, 170-178)
-        case EPI_RELU_DROP: return launch256_mt<sf32, EPI_RELU_DROP, true>(g, mt, s);
-        case EPI_DRELU_DROP: return launch256_mt<sf32, EPI_DRELU_DROP, true>(g, mt, s);
-        default: rgqa_set_error("gemm_x3: no kernel for epilogue %d", epi); return RGQA_ERR_ARG;
-    }
+    return launch256_epi<sf32, true, false>(NtEpis{}, "gemm_x3: no kernel", g, mt, s);
 }
 
 // ============================================================================ TN (wgrad), split-f32 operands
@@ -134,34 +68,7 @@ __global__ __launch_bounds__(T256_THREADS) void gemm_tn_x3_kernel(const GemmGrou
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wm = wave >> 2, wn = wave & 3;
-    // Block id -> tile.  The launcher sorts the problems by contraction length; problems of equal length form a class, and the ids of a class
-    // are re-dealt so that the blocks of one XCD (equal id mod 8, dispatched in id order) walk ONE contiguous run of the class's tile list:
-    // a run is a compact piece of one weight matrix - M-tiles of one N-tile first - whose tiles stream the same operand rows at the same time
-    // through that XCD's L2.  (Per problem instead of per class, the runs were 3-5 tiles: L2 hit rate 0.39.)  Every XCD gets an eighth of
-    // every class, so the XCDs stay balanced whatever the mix of lengths.
-    const int tile0 = blockIdx.x;
-    int p0 = 0;
-#pragma unroll
-    for (int i = 1; i < GEMM_MAX_PROBLEMS; ++i)
-        if (i < g.count && tile0 >= g.p[i].tile_start) p0 = i;
-    const int K0 = g.p[p0].K;
-    int c_lo = g.p[p0].tile_start, c_hi = g.total_tiles;
-#pragma unroll
-    for (int i = 0; i < GEMM_MAX_PROBLEMS; ++i)
-        if (i < g.count) {
-            if (g.p[i].K == K0) c_lo = min(c_lo, g.p[i].tile_start);
-            else if (g.p[i].K < K0) c_hi = min(c_hi, g.p[i].tile_start);
-        }
-    const int tile = c_lo + xcd_remap256(tile0 - c_lo, c_hi - c_lo);
-    int pi = 0;
-#pragma unroll
-    for (int i = 1; i < GEMM_MAX_PROBLEMS; ++i)
-        if (i < g.count && tile >= g.p[i].tile_start) pi = i;
-    const GemmProblem& P = g.p[pi];
-    const int tiles_m = cdiv(P.M, 256);
-    const int tix = tile - P.tile_start;
-    const int local = (tix % tiles_m) * P.tiles_n + (tix / tiles_m);
-    const int m0 = (local / P.tiles_n) * 256, n0 = (local % P.tiles_n) * 256;      // real coordinates
+    TN_TILE_MAP(g, 256, P, local, m0, n0)
     const int nkt = cdiv(P.K, X3_TK), ktail = P.K % X3_TK;
     const bf16_t* A = reinterpret_cast<const bf16_t*>(P.A);
     const bf16_t* B = reinterpret_cast<const bf16_t*>(P.B);
@@ -261,36 +168,7 @@ __global__ __launch_bounds__(T256_THREADS) void gemm_tn_x3_kernel(const GemmGrou
     };
     if (do_cs) kloop(std::true_type{}); else kloop(std::false_type{});
 
-    float* Cc = reinterpret_cast<float*>(P.C);
-    float* cs_out = P.colsum_out;
-    const int ldc = P.ldc;
-    constexpr bool accum = ACCUM != 0;
-    if (do_cs && (lane >> 4) == 0) {
-#pragma unroll
-        for (int rm = 0; rm < 8; ++rm) {
-            const int m = m0 + wm * 128 + rm * 16 + (lane & 15);
-            if (m < P.M) cs_out[m] = accum ? cs_out[m] + cs[rm][0] : cs[rm][0];
-        }
-    }
-    const int fr = lane & 15, fq = lane >> 4;
-#pragma unroll
-    for (int rm = 0; rm < 8; ++rm) {
-        const int m = m0 + wm * 128 + rm * 16 + fr;
-#pragma unroll
-        for (int tn = 0; tn < 4; ++tn) {
-            const int n = n0 + wn * 64 + tn * 16 + 4 * fq;
-            if (m < P.M && n < P.N) {
-                float* c = Cc + (size_t)m * ldc + n;
-                float v[4] = {acc[rm][tn][0], acc[rm][tn][1], acc[rm][tn][2], acc[rm][tn][3]};
-                if (n + 3 < P.N) {
-                    if (accum) { float o[4]; load4(c, o); v[0] += o[0]; v[1] += o[1]; v[2] += o[2]; v[3] += o[3]; }
-                    store4(c, v);
-                } else {
-                    for (int i = 0; i < P.N - n; ++i) c[i] = accum ? c[i] + v[i] : v[i];
-                }
-            }
-        }
-    }
+    TN_STORE_TILE(ACCUM, 8, P, do_cs, lane, wm, wn, m0, n0, acc, cs)
 }
 
 int launch_gemm_tn_x3(GemmGroup& g, hipStream_t s) {
@@ -303,15 +181,6 @@ int launch_gemm_tn_x3(GemmGroup& g, hipStream_t s) {
         RGQA_REQUIRE(x3_aligned(p.A, p.lda) && x3_aligned(p.B, p.ldb) && p.lda >= 32 && p.ldb >= 32, "gemm_tn_x3[%d]: operands must be 128-byte aligned with ld %% 32 == 0 (lda=%d ldb=%d)", i, p.lda, p.ldb);
         RGQA_REQUIRE((p.ldc % 4) == 0 && (((uintptr_t)p.C) & 15) == 0, "gemm_tn_x3[%d]: ldc %% 4 and 16-byte aligned C required", i);
     }
-    // longest contraction first: block ids are dispatched in order, so the dispatcher does LPT balancing
-    for (int i = 1; i < g.count; ++i)
-        for (int j = i; j > 0 && g.p[j].K > g.p[j - 1].K; --j) { GemmProblem t = g.p[j]; g.p[j] = g.p[j - 1]; g.p[j - 1] = t; }
-    static void* zero_line = nullptr;
-    if (zero_line == nullptr) {
-        RGQA_HIP(hipMalloc(&zero_line, 256));
-        RGQA_HIP(hipMemset(zero_line, 0, 256));
-    }
-    g.zeros = zero_line;
     constexpr int LDS_BYTES = 2 * 2 * X3_TK * X3_PITCH;
     static bool attr_set = false;
     if (!attr_set) {
@@ -319,7 +188,7 @@ int launch_gemm_tn_x3(GemmGroup& g, hipStream_t s) {
         RGQA_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_tn_x3_kernel<1>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES));
         attr_set = true;
     }
-    gemm_group_finalize(g, 256, 256);
+    if (int r = gemm_tn_prepare(g, 256, WN)) return r;
     if (epi == EPI_ACCUM) hipLaunchKernelGGL((gemm_tn_x3_kernel<1>), dim3(g.total_tiles), dim3(T256_THREADS), LDS_BYTES, s, g);
     else hipLaunchKernelGGL((gemm_tn_x3_kernel<0>), dim3(g.total_tiles), dim3(T256_THREADS), LDS_BYTES, s, g);
     RGQA_LAUNCH_CHECK("gemm_tn_x3_kernel");

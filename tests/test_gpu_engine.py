@@ -136,7 +136,10 @@ def oracle_run(cfgd, b, want_grads=True):
     return lg.detach(), pl.detach(), loss.item(), P
 
 
-@pytest.mark.parametrize("precision,tol,gtol", [("f32", 1e-4, 2e-3), ("bf16x3", 2e-4, 2e-3), ("bf16", 1.5e-2, 3.5e-2), ("bf16x3_fwd", 2e-4, 3.5e-2)])    # bf16 observed: logits 7.6e-3, worst tensor 1.7e-2
+X3_LOGITS_TOL = 2e-4     # bf16x3 logits against the oracle: test_medium_config_vs_oracle, test_split_f32_split_k_switch_reaches_the_cls_row_gemms
+
+
+@pytest.mark.parametrize("precision,tol,gtol", [("f32", 1e-4, 2e-3), ("bf16x3", X3_LOGITS_TOL, 2e-3), ("bf16", 1.5e-2, 3.5e-2), ("bf16x3_fwd", 2e-4, 3.5e-2)])    # bf16 observed: logits 7.6e-3, worst tensor 1.7e-2
 def test_medium_config_vs_oracle(precision, tol, gtol):
     """head size 64 / dims multiple of 64, so the bf16 MFMA kernels are the ones exercised.
     bf16 tolerance (2x observed): bf16 has 8 significant bits; through 7 blocks logits (|z|~1) land within 1.5e-2 abs, gradients within
@@ -1094,6 +1097,41 @@ def test_cls_only_tail_matches_full_rows(precision, train):
                 worst = max(worst, float((g1[name] - ref).abs().max()) / den)
         _report("cls tail vs all rows %s train=%s packed=%s" % (precision, train, packed), logits_max=float((lg1 - lg0).abs().max()), grad_rel_max=worst)
         assert worst <= 1e-6
+
+
+def test_split_f32_split_k_switch_reaches_the_cls_row_gemms():
+    """The split-K path of the split-f32 NT launcher (gemm_nt256.h, operand policy SplitKX3) has no operator-level entry: it is reached through the
+    engine's [CLS]-row GEMMs alone.  Smallest LXMERT at which it is taken - hidden 768 with 12 heads (head size 64), one layer of each kind, the
+    [CLS] tail on: the pooler (K = 768, 3 slices), the tail's FFN2 (K = 3072, 12) and the answer head (K = 1536, 6); every other launch is the same
+    in both arms.  rgqa_debug_set key 7 = 1 (slices folded in slice order) and = 0 (whole contractions) both meet the bf16x3 bound against the
+    oracle, differ in some bit (else the switch no longer reaches the path), and the split arm repeats bit for bit."""
+    from rgqa_amd import _lib
+    L = _lib.load()
+    cfgd = dict(vocab_size=512, hidden=768, heads=12, inter=3072, max_pos=64, type_vocab=2, l_layers=1, x_layers=1, r_layers=1,
+                feat_dim=64, pos_dim=4, num_answers=70)
+    B, T, O = 4, 8, 4
+    b = synth.synth_batch(B, T, O=O, F=cfgd["feat_dim"], NA=cfgd["num_answers"], vocab=cfgd["vocab_size"], seed=41, min_len=2)
+    lg_r = oracle_run(cfgd, b, want_grads=False)[0]
+    e = make_engine(cfgd, "bf16x3")
+    d = dev(b)
+    e.ensure_shape(B, T, O)
+    e.sync_weights()
+    arms = []
+    try:
+        assert L.rgqa_debug_set(8, 1) == 0
+        for split in (1, 0, 1):
+            assert L.rgqa_debug_set(7, split) == 0
+            arms.append(run(e, d)[0].clone())
+    finally:
+        L.rgqa_debug_set(7, 1)
+        L.rgqa_debug_set(8, -1)
+    on, off, again = arms
+    err_on, err_off = float((on.cpu() - lg_r).abs().max()), float((off.cpu() - lg_r).abs().max())
+    _report("split-f32 split-K on / off vs oracle", logits_max_on=err_on, logits_max_off=err_off, on_minus_off=float((on - off).abs().max()))
+    assert err_on < X3_LOGITS_TOL, err_on
+    assert err_off < X3_LOGITS_TOL, err_off
+    assert not torch.equal(on, off), "rgqa_debug_set key 7 does not reach the split-f32 split-K path"
+    assert torch.equal(on, again)
 
 
 @pytest.mark.parametrize("T", [5, 8])

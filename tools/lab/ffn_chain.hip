@@ -18,8 +18,6 @@
 #include <string.h>
 #include "gemm_nt256.h"
 
-bool gemm_nt256_eligible(const GemmGroup& g, int out_f32);      // csrc/gemm_mfma256.hip
-
 struct ChainArgs {
     GemmGroupNT g1, g2;          // finalized at tile heights 32 * MT1 / 32 * MT2; row-major tile numbering (tiles_n high half = 0)
     int* counters;               // zeroed before the launch: counters[cnt_base[p] + row block]
